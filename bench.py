@@ -19,11 +19,15 @@ order, so that ANY number of steps sees small and large pools in proportion (the
 inside a group everything happens as in the sequential loop: the first frame's k-means chain can only start once the pool is final,
 the chains of the others are enqueued ahead.
 
-Prints ONE compact JSON line on rank 0 as the LAST line of stdout (contract in the task statement; compact_line(): held under 4 KB by a CPU test):
-whole-job frames/s, roofline objects measured with HIP events inside the run, and a CPU baseline (the oracle timed on the host cores, rank 0, N = 1
-only).  Everything else -- notes, per-op tables, sweeps, the other configs' records -- goes to --details-file (default gpurun_out/bench_details.json),
-whose path the line carries.  Optional legs (--extras: cfg3, cfg4, closed-loop, backbone, corr-sweep) are not started once --budget-s seconds of wall
-time have passed; the default run takes about a minute.
+Prints ONE compact JSON line on rank 0 as the LAST line of stdout (compact_line(): held under 4 KB by a CPU test).  A plain run does only what the
+headline needs: set-up, --warmup steps, EXACTLY --steps timed steps (one region; --min-region-s repeats it), the outputs of the last timed step when
+--dump-outputs DIR is given, and the line: whole-job frames/s and `ms_per_step`.
+
+--full adds everything else, as before: HIP-event probes inside the timed region and the roofline objects built from them, the correlation kernel
+alone, the drained-queue enqueue cost, the exact-fp32 region, a CPU baseline (the oracle timed on the host cores, rank 0, N = 1 only) with a
+parity spot check, and the optional legs (--extras: cfg3, cfg4, closed-loop, backbone, corr-sweep; not started once --budget-s seconds of wall
+time have passed).  The full record -- notes, per-op tables, sweeps, the other configs' records -- goes to --details-file (with --full by default
+bench_out/bench_details.json), whose path the line carries; a --full run takes about a minute.
 """
 import argparse
 import os
@@ -34,6 +38,7 @@ import socket
 import subprocess
 import sys
 import time
+import zlib
 
 import numpy as np
 import torch
@@ -466,7 +471,7 @@ def launch_chains(wl, done=None):
 
 
 def frame_step(wl, gates, acts, dense_precision="split", pipeline=True, defer_corr=False):
-    """One frame of one sequence; returns (feat, gate outputs, pending correlation or None)."""
+    """One frame of one sequence; returns (feat, gate outputs, pending correlation or None, attention head)."""
     ref_emb, ref_lab = wl.refs()
     t = wl.t
     seg = probes = None
@@ -532,7 +537,7 @@ def frame_step(wl, gates, acts, dense_precision="split", pipeline=True, defer_co
     wl.advance()                                           # the walk moves on (a new group = a new pool state starts here)
     if wl.bank is None and wl.side is not None and pipeline and wl.t not in wl.ahead and not (wl.reuse_proxies and wl.cached_ahead is not None and wl.cached_ahead.R == wl.R):
         launch_chains(wl)                                  # the next frame's pool is final now: its chain starts under the other sequences' work
-    return feat, outs, aux["pending_correlation"]
+    return feat, outs, aux["pending_correlation"], head
 
 
 def _block_weights(mod):
@@ -663,7 +668,44 @@ def pmc_traffic_bytes(relpath):
 
 
 COMPACT_LIMIT = 4096           # bytes: the driver keeps an 8 KB tail of stdout; round 5's 23 KB line did not parse
-SCHEMA = 6                     # round 6: compact line + details file; host_enqueue_ms_per_step has its rounds-1-4 meaning again
+SCHEMA = 7                     # 7: a plain run carries the headline only (roofline / cpu_baseline / parity null), --full the rest; 6: compact line + details file
+DEFAULT_DETAILS = os.path.join("bench_out", "bench_details.json")     # --full without --details-file
+DUMP_LIMIT_BYTES = 60 << 20    # --dump-outputs: all .npy files together stay under 64 MB (headers included)
+
+
+def dump_sample_sizes(numels, budget):
+    """Elements kept of each array so that their sum stays within `budget`: smallest arrays first, each keeps min(its size, an equal share of
+    what is left) -- small arrays whole, the large ones sampled evenly."""
+    keep, left = [0] * len(numels), budget
+    order = sorted(range(len(numels)), key=lambda i: numels[i])
+    for j, i in enumerate(order):
+        keep[i] = min(numels[i], left // (len(order) - j))
+        left -= keep[i]
+    return keep
+
+
+def dump_sample_index(name, numel, k):
+    """A fixed, seeded, sorted sample of k of the numel flat indices of the output `name` (one random index in each of k equal strata):
+    the same for the same name and sizes on every run."""
+    if k >= numel:
+        return None
+    rng = np.random.RandomState(zlib.crc32(name.encode()))
+    stride = numel // k
+    return np.arange(k, dtype=np.int64) * stride + rng.randint(0, stride, size=k)
+
+
+def dump_outputs(path, named):
+    """--dump-outputs: write every (name, tensor) as path/<name>.npy in float32 (float64 stays float64), within DUMP_LIMIT_BYTES in all; an output
+    larger than its share is replaced by the fixed sample of dump_sample_index (flat, sorted indices)."""
+    os.makedirs(path, exist_ok=True)
+    dtypes = [np.dtype(np.float64 if t.dtype == torch.float64 else np.float32) for _, t in named]
+    keep = dump_sample_sizes([t.numel() * d.itemsize for (_, t), d in zip(named, dtypes)], DUMP_LIMIT_BYTES - 128 * len(named))   # bytes (128: .npy header)
+    for (name, t), k, d in zip(named, keep, dtypes):
+        out = t.detach()
+        idx = dump_sample_index(name, out.numel(), max(1, k // d.itemsize))
+        if idx is not None:
+            out = out.reshape(-1)[torch.from_numpy(idx).to(out.device)]
+        np.save(os.path.join(path, name + ".npy"), out.cpu().numpy().astype(d))
 
 
 def _pick(d, keys):
@@ -864,28 +906,39 @@ def main():
                     help="BASELINE.json configs[4]: run the sequence-sharded evaluation (eval_runner) over the ranks instead of the cfg2 step loop; "
                          "a fixed sequence set (strong scaling), --eval-scale of the 30 + 507 sequences")
     ap.add_argument("--eval-scale", type=float, default=0.03)
-    ap.add_argument("--min-region-s", type=float, default=1.0,
-                    help="the timed region of --steps steps is repeated until this many seconds have been timed (at most 15 regions); the line reports the MEDIAN region")
+    ap.add_argument("--min-region-s", type=float, default=0.0,
+                    help="the timed region of --steps steps is repeated until this many seconds have been timed (at most 15 regions); the line reports the MEDIAN "
+                         "region.  Default 0: one region of exactly --steps steps")
+    ap.add_argument("--full", action="store_true",
+                    help="measure more than the headline: in-run HIP-event probes and the roofline objects, the correlation kernel alone, the drained-queue "
+                         "enqueue cost, the exact-fp32 region, the CPU baseline + parity check, the optional legs of --extras, the details file")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (per sequence: the proto-mask features, the attention head and "
+                         "the 14 gate outputs) as DIR/<name>.npy, float32; at most 64 MB in all: an output larger than its share is a fixed, seeded "
+                         "sample of its flat elements (bench.dump_sample_index)")
     ap.add_argument("--extras", default="cfg3,cfg4",
-                    help="comma list of the optional legs, each written to the details file: cfg3, cfg4 (short regions of the other single-GPU configs, child "
+                    help="comma list of the optional legs of a --full run, each written to the details file: cfg3, cfg4 (short regions of the other single-GPU configs, child "
                          "processes, N = 1 only), closed-loop (the fixed-set sequence-sharded evaluation, any N), backbone (tools/backbone_e2e.py), "
                          "corr-sweep (the correlation kernel alone at 1 / 4 / 16 / 32 frames per launch); 'all' / 'none'.  A leg is skipped (and listed under "
                          "`skipped`) once --budget-s seconds of wall time have passed")
     ap.add_argument("--no-extras", action="store_true", help="same as --extras none")
     ap.add_argument("--budget-s", type=float, default=100.0, help="wall-time budget of the whole run in seconds: optional legs are not STARTED after it (0 = no limit)")
-    ap.add_argument("--details-file", default=os.path.join("gpurun_out", "bench_details.json"),
-                    help="where rank 0 writes the full record (notes, per-op tables, sweeps, other configs); the printed line carries the path")
+    ap.add_argument("--details-file", default=None,
+                    help="where rank 0 writes the full record (notes, per-op tables, sweeps, other configs); the printed line carries the path.  Default: "
+                         f"{DEFAULT_DETAILS} with --full, no file in a plain run")
     ap.add_argument("--strong-scale", type=float, default=0.12, help="share of the 537-sequence evaluation set used for the strong-scaling figure (64 sequences)")
     ap.add_argument("--eval-lanes", type=int, default=4,
                     help="sequences in flight per rank in the closed evaluation loop, each on its own HIP stream (one MI355X, 16-sequence set at the "
                          "end of round 3: 2 / 3 / 4 / 5 / 6 / 8 / 10 lanes = 226 / 241 / 245-251 / 242 / 239 / 234 / 225 frames/s; with the slower "
                          "kernels of the round's first half six lanes were best: 158 / 165 / 174 / 176 / 181 / 174 / 176)")
     args = ap.parse_args()
+    if args.details_file is None and args.full:
+        args.details_file = DEFAULT_DETAILS
     t_start = time.perf_counter()
     phases = {}
     global DENSE_SUBSAMPLE
     DENSE_SUBSAMPLE = max(1, args.cpu_dense_subsample)
-    extras = set() if (args.no_extras or args.extras == "none") else set(x.strip() for x in args.extras.split(",") if x.strip())
+    extras = set() if (not args.full or args.no_extras or args.extras == "none") else set(x.strip() for x in args.extras.split(",") if x.strip())
     if "all" in extras:
         extras = {"cfg3", "cfg4", "closed-loop", "backbone", "corr-sweep"}
     skipped = []
@@ -952,6 +1005,9 @@ def main():
             # the rank's sequences are synthesised and made resident first; the timed region starts at the barrier inside
             tot = eval_runner.eval_sharded(specs, rank, world, dev, barrier=barrier, lanes=max(1, args.eval_lanes))
             barrier()
+        if args.dump_outputs and rank == 0:                # what the run hands back: the job's reduced metric accumulators (identical on every rank)
+            dump_outputs(args.dump_outputs, [("eval_" + k, torch.tensor([float(tot[k])], dtype=torch.float64))
+                                             for k in ("frames", "objects", "mean_j", "mean_f")])
         el = torch.tensor([tot["loop_seconds_max"]], dtype=torch.float64)
         if rank == 0:
             line = {"metric": "frames/sec, AOC-Net matching + read-out + memory policy, sequence-sharded evaluation", "value": round(tot["frames"] / float(el.item()), 3),
@@ -1077,20 +1133,28 @@ def main():
     for wl in workloads:
         wl.timer = timer
     timer.serialize_dense = bool(args.dense_order) and not args.no_dense_order
-    timer.install(dict(dense_match_min=meta_dense, dense_match_min_split=meta_dense_split, proxy_corr_min=meta_proxy,
-                       proxy_corr_min_batched=meta_proxy_batched, proxy_corr_min_records=meta_proxy_records, kmeans_segmented=meta_kmeans, cluster_chain=meta_chain, film_scale=meta_film, cond_gate_pool=meta_cond))
+    probed = args.full or args.segments or bool(args.dump_timeline)       # HIP-event probes in the timed region (a plain run has none)
+    if probed or timer.serialize_dense:
+        timer.install(dict(dense_match_min=meta_dense, dense_match_min_split=meta_dense_split, proxy_corr_min=meta_proxy,
+                           proxy_corr_min_batched=meta_proxy_batched, proxy_corr_min_records=meta_proxy_records, kmeans_segmented=meta_kmeans, cluster_chain=meta_chain, film_scale=meta_film, cond_gate_pool=meta_cond))
     corr_stream = torch.cuda.Stream(device=dev) if batch_corr else None
+    last_step = []                                         # --dump-outputs: per sequence (features, attention head, gate outputs) of the last timed step
 
-    def run_steps(n):
-        for _ in range(n):
+    def run_steps(n, keep_last=False):
+        for i in range(n):
             pend = []
+            keep = keep_last and i == n - 1
+            if keep:
+                last_step.clear()
             for wl, st in zip(workloads, streams):
                 if n_streams > 1 or (args.cu_reserve > 0 and args.mask_main):
                     with torch.cuda.stream(st):
-                        _, _, p = frame_step(wl, gates, acts, args.dense, not args.no_pipeline, batch_corr)
+                        feat, outs, p, head = frame_step(wl, gates, acts, args.dense, not args.no_pipeline, batch_corr)
                 else:
-                    _, _, p = frame_step(wl, gates, acts, args.dense, not args.no_pipeline, batch_corr)
+                    feat, outs, p, head = frame_step(wl, gates, acts, args.dense, not args.no_pipeline, batch_corr)
                 pend.append(p)
+                if keep:
+                    last_step.append((feat, head, outs))
             if batch_corr:
                 # ONE correlation launch for the frames of all in-flight sequences; every sequence's stream joins it
                 done = hotpath.launch_correlations(pend, corr_stream)
@@ -1106,7 +1170,8 @@ def main():
         barrier()
         phase("setup_and_warmup", t_start)
         t_ph = time.perf_counter()
-        ops.dense_prune_stats(reset=True)     # counters of the coarse-then-rescore dense kernel over the timed regions (reads synchronise: outside them)
+        if probed:
+            ops.dense_prune_stats(reset=True)     # counters of the coarse-then-rescore dense kernel over the timed regions (reads synchronise: outside them)
         for wl in workloads:
             wl.count_r = True
         timer.want_segments = args.segments
@@ -1115,13 +1180,13 @@ def main():
         timer.probe_every = args.probe_every
         for i, wl in enumerate(workloads):
             wl.probe_phase = i * max(1, args.probe_every // 2)
-        timer.enabled = True                 # HIP events around every op, on the stream the op is launched on
+        timer.enabled = probed               # HIP events around every op, on the stream the op is launched on
         # EXACTLY --steps steps per region, bracketed by barrier + synchronize; regions are repeated (the group walk simply continues) until
         # --min-region-s seconds are covered, and the line reports the median region
         regions, enqueue = [], []
         while True:
             t0 = time.perf_counter()
-            run_steps(args.steps)
+            run_steps(args.steps, keep_last=bool(args.dump_outputs))
             enqueue.append(time.perf_counter() - t0)
             barrier()
             regions.append(time.perf_counter() - t0)
@@ -1133,15 +1198,25 @@ def main():
         timer.enabled = False
         for wl in workloads:
             wl.count_r = False
-        prune = ops.dense_prune_stats(reset=True)            # exactly the timed regions (the drained / profiled steps below are not counted)
+        prune = ops.dense_prune_stats(reset=True) if probed else None      # exactly the timed regions (the drained / profiled steps below are not counted)
         phase("timed_regions", t_ph)
+        if args.dump_outputs:
+            t_ph = time.perf_counter()
+            pre = f"rank{rank}_" if world > 1 else ""
+            named = []
+            for s, (feat, head, outs) in enumerate(last_step):
+                named += [(f"{pre}seq{s}_features", feat), (f"{pre}seq{s}_attention_head", head)]
+                named += [(f"{pre}seq{s}_{plan[0]}", x) for plan, x in zip(gates.plan(0, 0), outs)]
+            dump_outputs(args.dump_outputs, named)
+            last_step.clear()
+            phase("dump_outputs", t_ph)
         t_ph = time.perf_counter()
-        # What the enqueue calls of a step cost the host when nothing blocks: a few extra steps (outside the timed regions, the group walk simply
+        # --full: what the enqueue calls of a step cost the host when nothing blocks: a few extra steps (outside the timed regions, the group walk simply
         # continues) with the queues drained in front of each -- the wall time of run_steps(1) is then the CPU time of the step's enqueue calls,
         # while `enqueue` above also contains the time the host sits in the runtime waiting for room in full queues (it runs ~3 ms ahead)
         cpu_enqueue = []
         timer.want_segments = False               # (the drained steps below are not part of any reported bracket)
-        n_drained = max(8, min(40, syn.CONFIGS[args.config].frames - 1))       # one walk over the clip: steps with and without chain launches in proportion
+        n_drained = max(8, min(40, syn.CONFIGS[args.config].frames - 1)) if args.full else 0     # one walk over the clip: steps with and without chain launches in proportion
         for _ in range(n_drained):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -1161,8 +1236,9 @@ def main():
             with open(args.host_profile, "w") as f:
                 pstats.Stats(prof, stream=f).sort_stats("cumulative").print_stats(45)
                 pstats.Stats(prof, stream=f).sort_stats("tottime").print_stats(30)
-        host_cpu_enqueue_s = sum(cpu_enqueue) / len(cpu_enqueue)
-        phase("drained_steps", t_ph)
+        host_cpu_enqueue_s = sum(cpu_enqueue) / len(cpu_enqueue) if cpu_enqueue else None
+        if cpu_enqueue:
+            phase("drained_steps", t_ph)
     n_regions = len(regions)
 
     el = torch.tensor(regions, dtype=torch.float64, device=red_dev)
@@ -1198,7 +1274,7 @@ def main():
     # second, informational region (N = 1 only): a few steps with the exact-fp32 dense kernel (`--dense fp32`), so that the line also
     # carries the figure of the all-fp32 arithmetic next to the headline
     exact = None
-    if world == 1 and args.dense == "split" and args.exact_steps > 0:
+    if args.full and world == 1 and args.dense == "split" and args.exact_steps > 0:
         t_ph = time.perf_counter()
         with torch.no_grad():
             for wl in workloads:
@@ -1348,7 +1424,7 @@ def main():
                              frac=round(corr["gbs"] / PEAK_HBM_GBS, 4), traffic=None, avg_launch_ms=corr["avg_ms"], algorithmic_bytes_per_launch=corr["avg_bytes"],
                              frames_per_launch=n_streams if batch_corr else 1, in_run_frac=round(corr["gbs"] / PEAK_HBM_GBS, 4),
                              offline={"traffic_16_frames_per_launch": "profiles/r03_pmc_corr_records_B16.txt"})
-            if C == 100:
+            if C == 100 and args.full:
                 t_ph = time.perf_counter()
                 with torch.no_grad():
                     iso = correlation_roofline(cfg, mc, dev, batches=(1, 4, 16, 32) if leg("corr-sweep") else (1, 16), reps=20)
@@ -1363,7 +1439,7 @@ def main():
 
         cpu = None
         parity = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             t_ph = time.perf_counter()
             acts_cpu = [a.cpu() for a in acts]
             feats, rows, (emb2, lab2), tm, t_match, t_cal, threads, frame_s = cpu_baseline(cfg, mc, 1, gates, acts_cpu, runs=args.cpu_runs)
@@ -1410,7 +1486,7 @@ def main():
                     # a region = whole walks over the config's clip (frames - 1 steps each), like the cfg2 default: every pool size in proportion
                     walk = syn.CONFIGS[name].frames - 1
                     child_details = os.path.splitext(args.details_file)[0] + f"_{name}.json"
-                    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", name, "--steps", str(walk * (2 if walk < 10 else 1)), "--warmup", "3",
+                    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--config", name, "--steps", str(walk * (2 if walk < 10 else 1)), "--warmup", "3",
                                         "--min-region-s", "0.3", "--no-cpu-baseline", "--exact-steps", "0", "--no-extras", "--details-file", child_details],
                                        capture_output=True, text=True, timeout=300)
                     j = json.loads(r.stdout.strip().splitlines()[-1])
@@ -1478,9 +1554,10 @@ def main():
             # waits for room in full queues).  `host_enqueue_cpu_ms_per_step`: the CPU time of one step's enqueue calls, queues drained in front of the step
             # (mean over one walk of the clip, at most 40 steps; round 5 printed this under the first key)
             "host_enqueue_ms_per_step": round(host_enqueue_s / args.steps * 1e3, 3),
-            "host_enqueue_cpu_ms_per_step": round(host_cpu_enqueue_s * 1e3, 3),
+            "host_enqueue_cpu_ms_per_step": round(host_cpu_enqueue_s * 1e3, 3) if host_cpu_enqueue_s is not None else None,
             "probe_sampling": (f"the HIP-event brackets behind `kernels` / the roofline objects are placed on every {args.probe_every}-th frame of each sequence "
-                               "inside the timed region (on every frame -- --probe-every 1 -- their ~40 event records per frame cost 2.6 % frames/s)"),
+                               "inside the timed region (on every frame -- --probe-every 1 -- their ~40 event records per frame cost 2.6 % frames/s)" if probed
+                               else "none: a plain run places no HIP events in its timed region (--full does)"),
             **({"frame_segments_ms": segments} if segments else {}),
             "exact_fp32_dense_run": exact, "exact_fp32_value": exact["value"] if exact else None,
             "cfg3_value": other.get("cfg3", {}).get("value"), "cfg4_value": other.get("cfg4", {}).get("value"),
@@ -1494,9 +1571,10 @@ def main():
         full["wall_s"] = round(time.perf_counter() - t_start, 1)
         details_path = args.details_file
         try:
-            os.makedirs(os.path.dirname(os.path.abspath(details_path)), exist_ok=True)
-            with open(details_path, "w") as f:
-                json.dump(full, f, indent=1)
+            if details_path:
+                os.makedirs(os.path.dirname(os.path.abspath(details_path)), exist_ok=True)
+                with open(details_path, "w") as f:
+                    json.dump(full, f, indent=1)
         except OSError as e:                               # a read-only tree must not cost the line
             details_path = f"(not written: {e.__class__.__name__})"
         report = json.dumps(compact_line(full, details_path))

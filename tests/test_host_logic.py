@@ -498,66 +498,45 @@ def test_init_rows_draw_is_numpys_legacy_stream():
     assert np.array_equal(again, rows[2:])
 
 
-_INTEGRATION = r'''
-import importlib, sys
-sys.dont_write_bytecode = True                           # never write into /root/reference
-ref_root, repo = sys.argv[1], sys.argv[2]
-sys.path.insert(0, ref_root); sys.path.insert(0, repo)
-import aoc_amd
-# INTEGRATION.md section 1, verbatim
-sys.modules["networks.layers.matching"] = aoc_amd.matching
-sys.modules["networks.layers.attention"] = aoc_amd.attention
-sys.modules["networks.aoc.conditioning_layer"] = aoc_amd.conditioning_layer
-sys.modules["networks.p2t.conditioning_layer"] = aoc_amd.conditioning_layer
-sys.modules["networks.layers.gct"] = aoc_amd.gct          # the reference's gct.py imports networks.p2t.center_module, which it does not ship
-dm = importlib.import_module("networks.aoc.decoding_module")
-sys.modules["networks.p2t.decoding_module"] = dm          # aocnet.py:8 names a path the reference does not ship: its own decoder module
-an = importlib.import_module("networks.aoc.aocnet")
-# every name the two files import from the aliased modules is the mirror's object
-for name in ("global_matching", "global_matching_for_eval", "local_matching", "foreground2background", "global_matching_proxy", "local_matching_proxy",
-             "global_matching_cluster2", "global_matching_cluster", "global_matching_for_eval_cluster", "global_matching_for_eval_proxy"):
-    assert getattr(an, name) is getattr(aoc_amd.matching, name), name
-for name in ("calculate_attention_head", "calculate_attention_head_for_eval", "calculate_attention_head_p_m", "calculate_attention_head_for_eval_p_m"):
-    assert getattr(an, name) is getattr(aoc_amd.attention, name), name
-assert dm.IA_gate is aoc_amd.attention.IA_gate and dm.Bottleneck is aoc_amd.gct.Bottleneck and dm.GCT is aoc_amd.gct.GCT
-assert dm.conditioning_block is aoc_amd.conditioning_layer.conditioning_block and dm.conditioning_layer is aoc_amd.conditioning_layer.conditioning_layer
-assert an.CalibrationDecoding is dm.CalibrationDecoding and an.DynamicPreHead is dm.DynamicPreHead
-# the reference's decoder constructor with the arguments aocnet.py:37-42 passes (configs/resnet101_aocnet.py: 100 + 64, 400, 256, 64, 256).  Two names the
-# constructor reads are undefined in the reference (decoding_module.py:21 `unc_topk_ratio`, :30 `self.beta_percentage`): injected, nothing else is touched
-dm.unc_topk_ratio = 0.3
-dm.CalibrationDecoding.beta_percentage = 0.3
-dec = dm.CalibrationDecoding(in_dim=164, attention_dim=400, embed_dim=256, refine_dim=64, low_level_dim=256)
-A = aoc_amd
-assert isinstance(dec.IA1, A.attention.IA_gate) and dec.IA1.IA.weight.shape == (164, 400)
-assert isinstance(dec.CLB2, A.conditioning_layer.conditioning_block) and dec.CLB2.CL_3.mlp_layer.weight.shape == (400, 400)
-assert dec.CLB4.mlp_layer.weight.shape == (512, 2 * 512 + 400) and dec.CLB2.CL_1.beta_percentage == 0.3
-assert isinstance(dec.layer2, A.gct.Bottleneck) and isinstance(dec.GCT_sc, A.gct.GCT) and dec.GCT_sc.alpha.shape == (1, 512, 1, 1)
-assert dec.IA9.IA.weight.shape == (512, 400 + 512) and dec.IA10.IA.weight.shape == (320, 400 + 320) and dec.IA11.IA.weight.shape == (128, 400 + 128)
-# the gates of the decoder are the ones hotpath.CalibrationGates holds, name by name and shape by shape (a reference state_dict loads into either)
-gates = A.hotpath.CalibrationGates(A.hotpath.MatchingConfig())
-sd = dec.state_dict()
-for k, v in gates.state_dict().items():
-    assert k in sd and sd[k].shape == v.shape, k
-pre = dm.DynamicPreHead(in_dim=24, embed_dim=64)
-mine = A.hotpath.DynamicPreHead(in_dim=24, embed_dim=64)
-assert {k: tuple(v.shape) for k, v in pre.state_dict().items()} == {k: tuple(v.shape) for k, v in mine.state_dict().items()}
-print("INTEGRATION_OK", len(sd))
-'''
-
-_REF_ROOT = "/root/reference/AOC-Net/complete_project/AOCNet"
-
-
-@pytest.mark.skipif(not os.path.isdir(_REF_ROOT), reason="the reference only exists in the build container (nothing of it travels to the GPU box)")
-def test_reference_model_files_import_against_the_mirrors(tmp_path):
-    """INTEGRATION.md section 1 applied for real: with the sys.modules aliases in place the reference's OWN networks/aoc/aocnet.py and
-    networks/aoc/decoding_module.py import, every name they import resolves to a mirror, and the reference's decoder constructor
-    (decoding_module.py:10-93, arguments of aocnet.py:37-42) builds on the mirrors' constructors -- incl. the ``attention_dim=`` keyword it
-    passes to conditioning_block.  CPU only: constructors, no forward."""
-    script = tmp_path / "integration.py"
-    script.write_text(_INTEGRATION)
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-B", str(script), _REF_ROOT, repo], capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
-    assert r.returncode == 0 and "INTEGRATION_OK" in r.stdout, r.stdout + r.stderr
+def test_reference_model_files_import_against_the_mirrors():
+    """INTEGRATION.md section 1 applied to the reference's OWN networks/aoc/aocnet.py and networks/aoc/decoding_module.py, as recorded with the sys.modules
+    aliases in place by tests/golden/make_golden_integration.py (tests/golden/integration_decoder.json): every name the two files import from the aliased
+    modules is an object of that mirror; every constructor call the reference's decoder constructor makes of a mirror class (decoding_module.py:10-93,
+    arguments of aocnet.py:37-42, incl. the ``attention_dim=`` keyword it passes to conditioning_block) builds on the mirror's class with the parameter
+    shapes it built then; the gates hotpath.CalibrationGates holds are the decoder's, name by name and shape by shape (a reference state_dict loads into
+    either), and so is DynamicPreHead's state_dict.  CPU only: constructors, no forward."""
+    rec = json.load(open(os.path.join(ROOT, "tests", "golden", "integration_decoder.json")))
+    A = aoc_amd
+    mirrors = {n: getattr(A, n) for n in ("matching", "attention", "conditioning_layer", "gct")}
+    for fname, names in rec["imports"].items():
+        for name, mod in names.items():
+            assert inspect.isfunction(getattr(mirrors[mod], name, None)) or inspect.isclass(getattr(mirrors[mod], name, None)), (fname, name)
+    an, dm = rec["imports"]["aocnet"], rec["imports"]["decoding_module"]
+    for name in ("global_matching", "global_matching_for_eval", "local_matching", "foreground2background", "global_matching_proxy", "local_matching_proxy",
+                 "global_matching_cluster2", "global_matching_cluster", "global_matching_for_eval_cluster", "global_matching_for_eval_proxy"):
+        assert an[name] == "matching", name
+    for name in ("calculate_attention_head", "calculate_attention_head_for_eval", "calculate_attention_head_p_m", "calculate_attention_head_for_eval_p_m"):
+        assert an[name] == "attention", name
+    assert dm["IA_gate"] == "attention" and dm["Bottleneck"] == dm["GCT"] == "gct" and dm["conditioning_block"] == dm["conditioning_layer"] == "conditioning_layer"
+    assert rec["decoder_class"] == "CalibrationDecoding" and rec["prehead_is_reference_class"]
+    shapes = lambda m: {k: list(v.shape) for k, v in m.state_dict().items()}
+    built = {}
+    for c in rec["calls"]:
+        m = getattr(mirrors[c["module"]], c["cls"])(*c["args"], **c["kwargs"])
+        assert shapes(m) == c["state_dict"], c["attr"]
+        built[c["attr"]] = m
+    assert isinstance(built["IA1"], A.attention.IA_gate) and built["IA1"].IA.weight.shape == (164, 400)
+    assert isinstance(built["CLB2"], A.conditioning_layer.conditioning_block) and built["CLB2"].CL_3.mlp_layer.weight.shape == (400, 400)
+    assert built["CLB4"].mlp_layer.weight.shape == (512, 2 * 512 + 400) and built["CLB2"].CL_1.beta_percentage == 0.3
+    assert isinstance(built["layer2"], A.gct.Bottleneck) and isinstance(built["GCT_sc"], A.gct.GCT) and built["GCT_sc"].alpha.shape == (1, 512, 1, 1)
+    assert built["IA9"].IA.weight.shape == (512, 400 + 512) and built["IA10"].IA.weight.shape == (320, 400 + 320) and built["IA11"].IA.weight.shape == (128, 400 + 128)
+    sd = rec["state_dict"]["decoder"]
+    for c in rec["calls"]:                                  # the recorded calls are the decoder's own sub-modules
+        assert all(sd[c["attr"] + "." + k] == v for k, v in c["state_dict"].items()), c["attr"]
+    gates = A.hotpath.CalibrationGates(A.hotpath.MatchingConfig())
+    for k, v in gates.state_dict().items():
+        assert k in sd and sd[k] == list(v.shape), k
+    assert shapes(A.hotpath.DynamicPreHead(in_dim=24, embed_dim=64)) == rec["state_dict"]["DynamicPreHead"]
 
 
 def test_package_import_asks_for_enough_hardware_queues_unless_the_caller_chose():
@@ -677,6 +656,31 @@ def test_bench_reads_pmc_traffic_from_the_committed_file():
     t = bench.pmc_traffic_bytes("profiles/r06_pmc_dense_R6.txt")
     assert t is not None and abs(t - (2 * fetch + write) * 1024) < 1.0 and 2.0e8 < t < 6.0e8
     assert bench.pmc_traffic_bytes("profiles/does_not_exist.txt") is None
+
+
+def test_bench_dump_outputs_stay_within_the_limit_and_repeat(tmp_path, monkeypatch):
+    """--dump-outputs: small outputs are written whole, large ones as a fixed, seeded sample of their flat elements; all files together stay
+    under the limit, and the same outputs give the same files."""
+    import bench
+    import torch
+    # the cfg2 plan: two sequences x (features, attention head, 14 gate outputs) stay under 64 MB
+    numels = [4 * 24 * 121 * 213, 4 * 400] + [4 * c * 121 * 213 for c in (164, 256, 256, 320, 128)] + [4 * c * 61 * 107 for c in (512,) * 7 + (256,) * 2]
+    keep = bench.dump_sample_sizes([4 * n for n in numels * 2], bench.DUMP_LIMIT_BYTES)
+    assert sum(keep) <= bench.DUMP_LIMIT_BYTES < 64 * 10 ** 6 and keep[1] == 4 * 4 * 400 and min(keep) > 0
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1 << 20)
+    g = torch.Generator().manual_seed(0)
+    named = [("small", torch.randn(3, 5, generator=g)), ("wide", torch.randn(4, 300, 1000, generator=g)), ("f64", torch.randn(7, dtype=torch.float64, generator=g))]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), named)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["f64.npy", "small.npy", "wide.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 1 << 20
+    small, wide, f64 = (np.load(tmp_path / "a" / f) for f in ("small.npy", "wide.npy", "f64.npy"))
+    assert small.dtype == np.float32 and np.array_equal(small, named[0][1].numpy()) and f64.dtype == np.float64 and np.array_equal(f64, named[2][1].numpy())
+    idx = bench.dump_sample_index("wide", 4 * 300 * 1000, wide.size)
+    assert wide.ndim == 1 and 0 < wide.size < 4 * 300 * 1000 and np.all(np.diff(idx) > 0) and np.array_equal(wide, named[1][1].numpy().reshape(-1)[idx])
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
 
 
 def test_dense_seed_margin_covers_the_worst_case():
