@@ -52,6 +52,8 @@ def _dilate(b, r):
                 continue
             ys, ye = max(0, dy), min(H, H + dy)
             xs, xe = max(0, dx), min(W, W + dx)
+            if ys >= ye or xs >= xe:        # the offset leaves the map (|d| >= its size): a negative slice end would wrap around
+                continue
             out[ys - dy:ye - dy, xs - dx:xe - dx] |= b[ys:ye, xs:xe]
     return out
 
