@@ -34,7 +34,8 @@ constexpr float SP_SCALE = 1024.0f;            // 2^10
 constexpr float SP_QCONST = 32768.0f;          // query-side value of the norm slots: 2^15 * (-16 |r|^2) = -2^19 |r|^2
 constexpr float SP_UNSCALE = -1.0f / 524288.0f;   // d - |q|^2 = -2^-19 * acc
 constexpr int SP_TILE = 32;                    // reference pixels per MFMA tile
-constexpr int SP_NB = 4;                       // tiles per staged chunk (the product; dense_prune_kernel<4, 0, 2> stages two)
+constexpr int SP_NB = 4;                       // tiles per staged chunk of BOTH planes (development variants and dense_prune_q4_kernel)
+constexpr int SP_NB_HI = 8;                    // tiles per staged chunk of hi planes only (the product): the same bytes, twice the tiles
 constexpr int SP_NQ = 2;                       // 32-pixel query tiles per wave (stationary B operands in registers)
 
 static_assert(SP_NORM_SLOT + 4 <= SP_K && SP_NORM_SLOT / 16 == SP_KS - 1 && (SP_NORM_SLOT % 16) + 4 <= 8, "norm slots live in the low half of the last k-step");
@@ -264,21 +265,26 @@ __device__ __forceinline__ void glds4(const void *gsrc, uint32_t lds_dst) {
 }
 
 constexpr int SP_NBUF = 2;                                        // chunk buffers in LDS
-// LDS layout of a workgroup of NW waves that stages NB tiles per chunk
-__host__ __device__ constexpr int sp_chunk_bytes(int nb) { return nb * SP_TILE * SP_REC * 16; }     // NB = 4: 57344 (four tiles x 32 rows x 448 B, rows unpadded)
-__host__ __device__ constexpr int sp_ids_off(int nb) { return SP_NBUF * sp_chunk_bytes(nb); }       // 2 slots x (up to) 128 row ids
-__host__ __device__ constexpr int sp_obj_off(int nb) { return sp_ids_off(nb) + 2 * 512; }           // 4 slots x 64 tile objects (NB used)
-__host__ __device__ constexpr int sp_bnd_off(int nb) { return sp_obj_off(nb) + 4 * 256; }           // per (wave, query tile): 64 published bounds
-__host__ __device__ constexpr int sp_lds_bytes(int nw, int nb) { return sp_bnd_off(nb) + nw * SP_NQ * 256; }
+// LDS layout of a workgroup of NW waves that stages NB tiles per chunk; hi: a staged row is its hi plane only (224 B) instead of the record (448 B)
+__host__ __device__ constexpr int sp_row_chunks(bool hi) { return hi ? SP_HALF : SP_REC; }
+// 57344 both for NB = 8 hi planes (eight tiles x 32 rows x 224 B) and for NB = 4 records (four tiles x 32 rows x 448 B); rows unpadded
+__host__ __device__ constexpr int sp_chunk_bytes(int nb, bool hi = false) { return nb * SP_TILE * sp_row_chunks(hi) * 16; }
+__host__ __device__ constexpr int sp_ids_off(int nb, bool hi = false) { return SP_NBUF * sp_chunk_bytes(nb, hi); }
+// row ids: records 2 slots x (up to) 128 ids; hi planes 3 slots x 256 ids (the rescoring reads the CURRENT chunk's ids while the next two are in the ring)
+__host__ __device__ constexpr int sp_obj_off(int nb, bool hi = false) { return sp_ids_off(nb, hi) + (hi ? 3 * 1024 : 2 * 512); }
+__host__ __device__ constexpr int sp_bnd_off(int nb, bool hi = false) { return sp_obj_off(nb, hi) + 4 * 256; }      // before it: 4 slots x 64 tile objects (NB used)
+__host__ __device__ constexpr int sp_lds_bytes(int nw, int nb, bool hi = false) { return sp_bnd_off(nb, hi) + nw * SP_NQ * 256; }   // per (wave, query tile): 64 published bounds
+static_assert(sp_chunk_bytes(SP_NB_HI, true) == sp_chunk_bytes(SP_NB) && sp_lds_bytes(8, SP_NB_HI, true) == 122880, "the hi-plane ring has the size of the record ring; 120 KiB per workgroup");
 constexpr int SP_TILE_SLACK = 2;                                  // the plan always holds an empty tile after the last one
 
 // Coarse-then-rescore.  Block = 8 waves x 2 query tiles (512 query pixels; both planes of their records are the stationary B
-// operands, 112 VGPR); the object-sorted reference tiles stream through two LDS chunk buffers (4 tiles each, both planes, A
-// operands).  Grid = (query blocks, tile splits).  Per (reference tile, query tile) ONE pass of 7 MFMAs gives
+// operands, 112 VGPR); the object-sorted reference tiles stream through two LDS chunk buffers (HI, the product: 8 tiles each, hi planes
+// only; development variants: 4 or 2 tiles each, both planes; A operands).  Grid = (query blocks, tile splits).  Per (reference tile, query tile) ONE pass of 7 MFMAs gives
 // coarse = 2^20 (qh.rh - |r|^2/2); the exact three-product value differs from it by the qh.rl + ql.rh terms, bounded by
 // eps(q) = 2^10 |q| max|r| (1 + margins): a pair whose coarse value plus eps is below the best EXACT value already known for that
 // (query pixel, object) cannot hold the maximum and is skipped; any other pair gets the 14 MFMAs of the two cross terms added onto the
-// same accumulators (everything is on chip: no memory latency on that path), which is then exactly the three-product value.  The best
+// same accumulators, which is then exactly the three-product value (HI: the reference tile's lo plane, which only these 5 % of the pairs
+// read, is fetched from the records in global memory at that point, see the rescoring path; otherwise everything is on chip).  The best
 // exact values live in gbest[pixel][object] (atomicMax on an order-preserving encoding) and are shared by all splits and by the
 // workgroups of later rounds, so the bound tightens after the first few tiles anywhere on the chip.  The true maximum always survives
 // (coarse + eps >= exact >= every bound) and its value does not depend on what else was evaluated: the result is deterministic
@@ -286,9 +292,17 @@ constexpr int SP_TILE_SLACK = 2;                                  // the plan al
 //
 // Data movement: the chunk of step s + 1 is fetched by LDS-DMA while step s computes (no staging registers, no ds_write pass); its row
 // ids (and the tiles' objects) were themselves DMA'd one step earlier, and the bounds other workgroups published come in the same
-// way.  LDS rows are unpadded (448 B); chunk c of row r sits at position c ^ ((r >> 3) & 3), which makes every ds_read_b128 of an A
-// fragment conflict-free -- the swizzle is applied on the SOURCE address of the DMA, whose destination is lane-linear.  The transfers
-// are asm statements that hipcc neither counts nor drains; one vmcnt(0) + barrier per step (4 tiles) publishes them.
+// way.  LDS rows are unpadded (HI: 224 B, the 14 hi chunks of the 448-byte record; else the record); chunk c of row r sits at position
+// c ^ ((r >> 3) & 1) (records: & 3), which makes every ds_read_b128 of an A fragment conflict-free (derivation at SWZ_MASK) -- the swizzle is
+// applied on the SOURCE address of the DMA, whose destination is lane-linear.  The transfers are asm statements that hipcc neither counts
+// nor drains; one vmcnt(0) + barrier per step publishes them.
+//
+// Why hi planes only (profiles/dense_hi_ring_ab.txt): what a step costs apart from its tiles -- issuing the 7 transfers per wave, vmcnt(0), the
+// bound read-back, the barrier at which the waves' rescoring imbalance meets -- was 850 of ~2 290 cycles per tile with four-tile steps; the lo
+// plane was half of every transfer and of the ring and is read by the rescoring path only.  The same 2 x 56 KiB now hold eight tiles per step.
+// LDS per workgroup: 2 x 57 344 (ring) + 3 x 1 024 (row ids: the chunk in use, the one being fetched, the one after) + 4 x 256 (tile objects)
+// + 16 x 256 (bounds) = 120 KiB.  The published bounds are taken in once per step as before, i.e. every eight tiles now: the rescored share of
+// the bench's R = 6 pools went from 4.9 to 5.1 %; a refresh half way through the step brought it back and cost more than it saved (same file).
 //
 // Checkpoint (CKPT = 3 or 4, development build only; 0 = off = the product: built and measured in round 5, correct and SLOWER, see split_ckpt()).  After CKPT of the 7 k-steps -- order 6, 0, 1, 2, ...: the norm slots first -- the
 // accumulator holds 2^20 (P - |r|^2 / 2) with P the hi x hi product over the channels seen so far.  What the remaining k-steps can add is at most
@@ -299,7 +313,7 @@ constexpr int SP_TILE_SLACK = 2;                                  // the plan al
 // MFMA whose A fragment is zero except for the negated norm slot, then continues as before.  The bound is rigorous (the products of the fp16
 // values are exact, the norms are rounded up, the accumulations' roundings are inside eps), so the set of discarded pairs can never contain
 // the maximum: same results as CKPT = 0, deterministic as before (a pair's value does not depend on what else was evaluated).
-template <int NW, int CKPT, int NB = SP_NB>
+template <int NW, int CKPT, int NB = SP_NB, bool HI = false>
 __global__ __launch_bounds__(NW * 64, NB == 2 ? 2 : 1) void dense_prune_kernel(const uint4 *__restrict__ qrec, const float *__restrict__ q2, int64_t m,
                                                                      const uint4 *__restrict__ prec, const int32_t *__restrict__ tile_rows,
                                                                      const int32_t *__restrict__ tile_obj, const int32_t *__restrict__ n_tiles_ptr,
@@ -315,9 +329,19 @@ __global__ __launch_bounds__(NW * 64, NB == 2 ? 2 : 1) void dense_prune_kernel(c
     (void)dbg_arg;
 #endif
     extern __shared__ __attribute__((aligned(16))) uint4 lds4[];
-    static_assert(SP_NQ == 2 && ((NB == 4 && (NW == 8 || NW == 4)) || (NB == 2 && NW == 4)),
-                  "the step structure below is written for 4 tiles x 2 query tiles x 8 (or 4) waves, or 2 tiles x 2 query tiles x 4 waves (two workgroups per CU)");
-    constexpr int SP_CHUNK_BYTES = sp_chunk_bytes(NB), SP_IDS_OFF = sp_ids_off(NB), SP_OBJ_OFF = sp_obj_off(NB), SP_BND_OFF = sp_bnd_off(NB);
+    static_assert(SP_NQ == 2 && (HI ? (NB == 8 && NW == 8 && CKPT == 0) : ((NB == 4 && (NW == 8 || NW == 4)) || (NB == 2 && NW == 4))),
+                  "the step structure below is written for 8 hi-plane tiles x 2 query tiles x 8 waves, for 4 record tiles x 2 query tiles x 8 (or 4) waves, or for "
+                  "2 record tiles x 2 query tiles x 4 waves (two workgroups per CU)");
+    constexpr int SP_CHUNK_BYTES = sp_chunk_bytes(NB, HI), SP_IDS_OFF = sp_ids_off(NB, HI), SP_OBJ_OFF = sp_obj_off(NB, HI), SP_BND_OFF = sp_bnd_off(NB, HI);
+    constexpr int ROW_CHUNKS = sp_row_chunks(HI), ROW_BYTES = ROW_CHUNKS * 16, TILE_BYTES = SP_TILE * ROW_BYTES;      // a staged row / tile
+    constexpr int IDS_SLOTS = HI ? 3 : 2, IDS_SLOT_BYTES = HI ? 1024 : 512;
+    // Swizzle of the unpadded LDS rows: chunk c of row r sits at position c ^ ((r >> 3) & SWZ_MASK).  A ds_read_b128 is served in groups of 16 lanes
+    // (rows {0-3, 12-15, 20-27} and {4-11, 16-19, 28-31} of the tile, one k-half each) that must hit 16 different 16-byte columns of the 256-byte bank
+    // line.  448-byte rows: column = (12 r + position) mod 16, four rows of a group share 12 r mod 16 and the two low position bits tell them apart
+    // (mask 3).  224-byte rows: column = (14 r + position) mod 16 = (position - 2 r) mod 16; the eight residues of r mod 8 give the eight even
+    // offsets, each shared by TWO rows of a group -- (r, r + 24) or (r, r + 8), with r >> 3 = 0 | 3 or 1 | 2 -- and bit 0 of the position, flipped
+    // by bit 3 of the row, puts one of the two on the odd column (mask 1; positions 2 k and 2 k + 1 swap, so a row stays inside its 14 chunks).
+    constexpr int SWZ_MASK = HI ? 1 : 3;
     static_assert(CKPT == 0 || CKPT == 3 || CKPT == 4, "checkpoint after 3 or 4 k-steps (rest norms in slots 104 / 105), or none");
     constexpr int SP_DMA_PER_WAVE = SP_CHUNK_BYTES / 1024 / NW;      // 7 (14) wave-wide 1 KiB transfers per wave and chunk
     constexpr int W_ID0 = NW / 2, W_ID1 = NW - 1, W_OBJ = 1;         // the waves that also fetch the row ids / the tiles' objects
@@ -392,20 +416,27 @@ __global__ __launch_bounds__(NW * 64, NB == 2 ? 2 : 1) void dense_prune_kernel(c
         eps[iq] = (1026.0f * (qn * plmax + ql * pmax) + 8.0f * pmax * pmax + (CKPT != 0 ? 16.0f * qn * pmax : 0.0f) + 8.0f) * ((dbg & 64) ? 0.4f : 1.0f);
     }
 
-    // ---- DMA plan of this wave: transfer k of a chunk fills the LDS slots [64 (7 wave + k), +64); slot j holds row j / 28, position j % 28.
-    // Packed per transfer: row of the chunk (0..127) in the high half, source byte offset of that position's chunk in the low half.
+    // ---- DMA plan of this wave: transfer k of a chunk fills the LDS slots [64 (7 wave + k), +64); slot j holds row j / 28, position j % 28 (hi
+    // planes only: row j / 14, position j % 14).  Packed per transfer: row of the chunk (0..127 / 0..255) in the high half, source byte offset
+    // of that position's chunk in the low half.
     uint32_t dma_plan[SP_DMA_PER_WAVE];
 #pragma unroll
     for (int k = 0; k < SP_DMA_PER_WAVE; ++k) {
         const int j = (wave * SP_DMA_PER_WAVE + k) * 64 + lane;
-        const int r = j / SP_REC, pos = j - r * SP_REC;
-        dma_plan[k] = ((uint32_t)r << 16) | (uint32_t)((pos ^ ((r >> 3) & 3)) * 16);
+        const int r = j / ROW_CHUNKS, pos = j - r * ROW_CHUNKS;
+        dma_plan[k] = ((uint32_t)r << 16) | (uint32_t)((pos ^ ((r >> 3) & SWZ_MASK)) * 16);
     }
     const char *prec_bytes = reinterpret_cast<const char *>(prec);
     auto dma_meta = [&](int chunk) {            // row ids (two waves, two tiles each) and tile objects (one wave) of a chunk -> their rings
         // tile i of the split is tile by + i ns of the plan; past the end everything reads the (always present) empty tile n_tiles
         const int i0 = chunk * NB;
-        if (wave == W_ID0 || (NB == 4 && wave == W_ID1)) {
+        if constexpr (HI) {
+            // eight tiles x 32 ids = 1 KiB: ONE 16-byte transfer of one wave (lane -> tile lane / 8, ids 4 (lane % 8) .. + 3)
+            if (wave == W_ID0) {
+                const int t = min(by + (i0 + (lane >> 3)) * ns, n_tiles);
+                glds16(tile_rows + (size_t)t * SP_TILE + (lane & 7) * 4, lds_base + SP_IDS_OFF + (chunk % IDS_SLOTS) * IDS_SLOT_BYTES);
+            }
+        } else if (wave == W_ID0 || (NB == 4 && wave == W_ID1)) {
             const int i = i0 + (wave == W_ID1 ? 2 : 0) + (lane >> 5);
             const int t = min(by + i * ns, n_tiles);
             glds4(tile_rows + (size_t)t * SP_TILE + (lane & 31), lds_base + SP_IDS_OFF + (chunk & 1) * 512 + (wave == W_ID1 ? 256 : 0));
@@ -413,7 +444,7 @@ __global__ __launch_bounds__(NW * 64, NB == 2 ? 2 : 1) void dense_prune_kernel(c
         if (wave == W_OBJ) glds4(tile_obj + min(by + (i0 + (lane & (NB - 1))) * ns, n_tiles), lds_base + SP_OBJ_OFF + (chunk & 3) * 256);
     };
     auto dma_rows = [&](int chunk) {            // the chunk's records -> buffer chunk % 2 (its ids must have landed and been published)
-        const int32_t *ids = reinterpret_cast<const int32_t *>(lds_bytes + SP_IDS_OFF + (chunk & 1) * 512);
+        const int32_t *ids = reinterpret_cast<const int32_t *>(lds_bytes + SP_IDS_OFF + (chunk % IDS_SLOTS) * IDS_SLOT_BYTES);
         const uint32_t dst = lds_base + (uint32_t)(chunk % SP_NBUF) * SP_CHUNK_BYTES + (uint32_t)(wave * SP_DMA_PER_WAVE) * 1024u;
         int id[SP_DMA_PER_WAVE];
 #pragma unroll
@@ -478,10 +509,11 @@ __global__ __launch_bounds__(NW * 64, NB == 2 ? 2 : 1) void dense_prune_kernel(c
 
     // A fragment addressing: chunk index e + h (e even, compile time) of row (tile, col) sits at position (e & ~3) + (((e & 2) + h) ^ x),
     // x = (col >> 3) & 3: two per-lane byte offsets cover it
-    const int xs = (col >> 3) & 3;
-    const uint32_t row_off = (uint32_t)col * (SP_REC * 16);
-    const uint32_t sw0 = row_off + (uint32_t)((h ^ xs) * 16), sw2 = row_off + (uint32_t)(((2 + h) ^ xs) * 16);
-    auto frag = [&](const char *tile_base, int e) -> f16x8 {       // e: even chunk index (2 ks for the hi plane, 14 + 2 ks for the lo plane)
+    // (hi planes only, x = (col >> 3) & 1: position (e & ~1) + (h ^ x), ONE per-lane offset)
+    const int xs = (col >> 3) & SWZ_MASK;
+    const uint32_t row_off = (uint32_t)col * ROW_BYTES;
+    const uint32_t sw0 = row_off + (uint32_t)((h ^ xs) * 16), sw2 = HI ? sw0 + 32u : row_off + (uint32_t)(((2 + h) ^ xs) * 16);
+    auto frag = [&](const char *tile_base, int e) -> f16x8 {       // e: even chunk index (2 ks for the hi plane, 14 + 2 ks for the lo plane of a staged record)
         const uint32_t off = ((e & 2) ? sw2 : sw0) + (uint32_t)((e & ~3) * 16);
         return __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4 *>(tile_base + off));
     };
@@ -495,6 +527,8 @@ __global__ __launch_bounds__(NW * 64, NB == 2 ? 2 : 1) void dense_prune_kernel(c
         // the barrier that ended step s - 1 published)
         const unsigned long long t_s0 = stamp();
         const int4 objs = *reinterpret_cast<const int4 *>(lds_bytes + SP_OBJ_OFF + (s & 3) * 256);
+        int4 objs_b = make_int4(0, 0, 0, 0);                           // tiles 4..7 of a chunk of hi planes
+        if constexpr (NB == 8) objs_b = *reinterpret_cast<const int4 *>(lds_bytes + SP_OBJ_OFF + (s & 3) * 256 + 16);
         const int bound_obj = (dbg & 32) ? -3 : cur;
         if (!(dbg & 32)) dma_bound();
         dma_meta(s + 2);
@@ -505,13 +539,17 @@ __global__ __launch_bounds__(NW * 64, NB == 2 ? 2 : 1) void dense_prune_kernel(c
         const int n_here = min(NB, n_mine - s * NB);
         // the first two A fragments of a tile are requested while the previous tile's epilogue runs
         f16x8 pre0 = frag(chunk_base, 2 * ks_of(0)), pre1 = frag(chunk_base, 2 * ks_of(1));
-        // the four tiles' objects in one scalar (objects are < 256): two SALU operations per tile instead of a chain of selects
-        const uint32_t objs_packed = (uint32_t)__builtin_amdgcn_readfirstlane((objs.x & 0xff) | ((objs.y & 0xff) << 8) | ((objs.z & 0xff) << 16) | ((objs.w & 0xff) << 24));
+        // the tiles' objects in one 64-bit scalar (objects are < 256): two SALU operations per tile instead of a chain of selects
+        const uint32_t objs_lo = (uint32_t)__builtin_amdgcn_readfirstlane((objs.x & 0xff) | ((objs.y & 0xff) << 8) | ((objs.z & 0xff) << 16) | ((objs.w & 0xff) << 24));
+        const uint32_t objs_hi = (uint32_t)__builtin_amdgcn_readfirstlane((objs_b.x & 0xff) | ((objs_b.y & 0xff) << 8) | ((objs_b.z & 0xff) << 16) | ((objs_b.w & 0xff) << 24));
+        const uint64_t objs_packed = NB == 8 ? ((uint64_t)objs_hi << 32) | objs_lo : (uint64_t)objs_lo;
+        // hi planes only: the current chunk's row ids (the rescoring path addresses the lo planes in global memory with them)
+        const int32_t *ids_now = reinterpret_cast<const int32_t *>(lds_bytes + SP_IDS_OFF + (s % IDS_SLOTS) * IDS_SLOT_BYTES);
         t_prev = stamp();
         cyc[4] += t_prev - t_s0;
 #pragma unroll 1
         for (int t = 0; t < n_here; ++t) {
-            const char *tile_base = chunk_base + t * (SP_TILE * SP_REC * 16);
+            const char *tile_base = chunk_base + t * TILE_BYTES;
             const int o = (int)((objs_packed >> (8 * t)) & 0xffu);
             if (o != cur) switch_object(o);
             const unsigned long long t_0 = stamp();
@@ -535,8 +573,8 @@ __global__ __launch_bounds__(NW * 64, NB == 2 ? 2 : 1) void dense_prune_kernel(c
                         acc[iq] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[kk % 3], bh[iq][ks_of(kk)], acc[iq], 0, 0, 0);
                 }
                 if (t + 1 < n_here) {
-                    pre0 = frag(tile_base + SP_TILE * SP_REC * 16, 2 * ks_of(0));
-                    pre1 = frag(tile_base + SP_TILE * SP_REC * 16, 2 * ks_of(1));
+                    pre0 = frag(tile_base + TILE_BYTES, 2 * ks_of(0));
+                    pre1 = frag(tile_base + TILE_BYTES, 2 * ks_of(1));
                 }
             } else {
                 // phase 1: the first CKPT k-steps (k-step 6 carries the norm slots AND the bound's rank-1 term)
@@ -553,7 +591,7 @@ __global__ __launch_bounds__(NW * 64, NB == 2 ? 2 : 1) void dense_prune_kernel(c
                     for (int iq = 0; iq < SP_NQ; ++iq)
                         acc[iq] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[kk % 3], bh[iq][ks_of(kk)], acc[iq], 0, 0, 0);
                 }
-                if (t + 1 < n_here) pre0 = frag(tile_base + SP_TILE * SP_REC * 16, 2 * ks_of(0));
+                if (t + 1 < n_here) pre0 = frag(tile_base + TILE_BYTES, 2 * ks_of(0));
                 // checkpoint: can any pair of this (reference tile, query tile) still reach what is known for its pixel?  (wave-uniform)
 #pragma unroll
                 for (int iq = 0; iq < SP_NQ; ++iq) {
@@ -604,45 +642,69 @@ __global__ __launch_bounds__(NW * 64, NB == 2 ? 2 : 1) void dense_prune_kernel(c
             t_prev = t_2;
             if ((want[0] || want[1]) && !(dbg & 2)) {
                 n_any += 1;
+                // hi planes only: the tile's lo plane comes from the records in global memory (L2 / Infinity Cache resident: every workgroup of the
+                // split streams the same tiles), once per tile for both query tiles -- seven 16-byte loads per lane, row = the CURRENT chunk's id
+                // (slot s % 3 of the id ring; dma_meta(s + 2) and dma_rows(s + 1) use the other two slots during this step) -- and is waited for
+                // right here with an explicit vmcnt(0).  Outstanding at that point: the seven loads; in front of them this step's LDS-DMA statements
+                // (2 bounds, up to 2 meta, 7 rows: asm that hipcc does not count) unless an earlier tile of the step has drained them already, and
+                // fire-and-forget atomics of earlier rescorings.  vmcnt retires in issue order, so any wait for the loads covers all of these:
+                // correct, and a rescoring early in a step waits for the next chunk to land as well (the end of the step waits for it anyway).  No
+                // LDS-DMA is issued between the loads and their use.  Why not hipcc's own counted waits in front of each MFMA (vmcnt(6) ... (0)): the
+                // two rescorings are separate branches, its wait insertion merges the paths behind them, cannot know that one of the two always
+                // runs, keeps the loads pending around the tile loop and drains vmcnt(0) -- i.e. this step's DMA -- in front of EVERY tile's
+                // decision.  The explicit wait costs a rescoring tile the ~100 cycles of the first LDS read and MFMA that could have overlapped.
+                // Register arrays are indexed by unrolled constants only.
+                f16x8 alg[SP_KS];
+                auto load_lo = [&]() {
+                    if constexpr (HI) {
+                        const int id = ids_now[t * SP_TILE + col];
+                        const uint4 *lo = reinterpret_cast<const uint4 *>(prec_bytes + (size_t)(uint32_t)max(id, 0) * (SP_REC * 16) + SP_HALF * 16) + h;
 #pragma unroll
-                for (int iq = 0; iq < SP_NQ; ++iq) {
-                    if (want[iq]) {
-                        // cross terms: acc += rh.ql + rl.qh (one chain of 14 MFMAs), then the exact maximum
-                        n_rescored += 1;
-                        if (dbg & 65536) {                                 // rescored pairs of the objects 0, 1, 2 (read back like the stamps).  STATIC indices:
-                            if (cur == 0) cyc[0] += 1;                     // `cyc[cur]` made hipcc index the register array dynamically and the kernel -- whose
-                            else if (cur == 1) cyc[1] += 1;                // DMA statements are hand-written asm around m0 -- returned wrong minima for nine
-                            else if (cur == 2) cyc[2] += 1;                // objects even with the bit off (caught by test_kmeans_bit_exact_with_the_single_pass_tail)
-                        }
-                        f16x8 ah[3], al[3];
-#pragma unroll
-                        for (int kk = 0; kk < 2; ++kk) {
-                            ah[kk] = frag(tile_base, 2 * ks_of(kk));
-                            al[kk] = frag(tile_base, 2 * SP_KS + 2 * ks_of(kk));
-                        }
-#pragma unroll
-                        for (int kk = 0; kk < SP_KS; ++kk) {
-                            if (kk + 2 < SP_KS) {
-                                ah[(kk + 2) % 3] = frag(tile_base, 2 * ks_of(kk + 2));
-                                al[(kk + 2) % 3] = frag(tile_base, 2 * SP_KS + 2 * ks_of(kk + 2));
-                            }
-                            acc[iq] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[kk % 3], bl[iq][ks_of(kk)], acc[iq], 0, 0, 0);
-                            acc[iq] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[kk % 3], bh[iq][ks_of(kk)], acc[iq], 0, 0, 0);
-                        }
-                        const float ex = max16(acc[iq]);
-                        if (ex > best[iq]) {
-                            best[iq] = ex;
-                            if (ex > shared[iq] && !(dbg & 1)) atomicMax(gbest + grow[iq] + cur, ord_enc(ex));      // fire and forget
-                        }
+                        for (int kk = 0; kk < SP_KS; ++kk) alg[kk] = __builtin_bit_cast(f16x8, lo[2 * ks_of(kk)]);
+                        __builtin_amdgcn_s_waitcnt(0x0f70);                 // vmcnt(0)
                     }
-                }
+                };
+                auto rescore = [&](auto iq_c) {
+                    constexpr int iq = decltype(iq_c)::value;
+                    // cross terms: acc += rh.ql + rl.qh (one chain of 14 MFMAs), then the exact maximum
+                    n_rescored += 1;
+                    if (dbg & 65536) {                                 // rescored pairs of the objects 0, 1, 2 (read back like the stamps).  STATIC indices:
+                        if (cur == 0) cyc[0] += 1;                     // `cyc[cur]` made hipcc index the register array dynamically and the kernel -- whose
+                        else if (cur == 1) cyc[1] += 1;                // DMA statements are hand-written asm around m0 -- returned wrong minima for nine
+                        else if (cur == 2) cyc[2] += 1;                // objects even with the bit off (caught by test_kmeans_bit_exact_with_the_single_pass_tail)
+                    }
+                    f16x8 ah[3], al[3];
+#pragma unroll
+                    for (int kk = 0; kk < 2; ++kk) {
+                        ah[kk] = frag(tile_base, 2 * ks_of(kk));
+                        if constexpr (!HI) al[kk] = frag(tile_base, 2 * SP_KS + 2 * ks_of(kk));
+                    }
+#pragma unroll
+                    for (int kk = 0; kk < SP_KS; ++kk) {
+                        if (kk + 2 < SP_KS) {
+                            ah[(kk + 2) % 3] = frag(tile_base, 2 * ks_of(kk + 2));
+                            if constexpr (!HI) al[(kk + 2) % 3] = frag(tile_base, 2 * SP_KS + 2 * ks_of(kk + 2));
+                        }
+                        acc[iq] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[kk % 3], bl[iq][ks_of(kk)], acc[iq], 0, 0, 0);
+                        if constexpr (HI) acc[iq] = __builtin_amdgcn_mfma_f32_32x32x16_f16(alg[kk], bh[iq][ks_of(kk)], acc[iq], 0, 0, 0);
+                        else acc[iq] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[kk % 3], bh[iq][ks_of(kk)], acc[iq], 0, 0, 0);
+                    }
+                    const float ex = max16(acc[iq]);
+                    if (ex > best[iq]) {
+                        best[iq] = ex;
+                        if (ex > shared[iq] && !(dbg & 1)) atomicMax(gbest + grow[iq] + cur, ord_enc(ex));      // fire and forget
+                    }
+                };
+                load_lo();
+                if (want[0]) rescore(std::integral_constant<int, 0>{});
+                if (want[1]) rescore(std::integral_constant<int, 1>{});
                 t_prev = stamp();
                 cyc[2] += t_prev - t_2;
             }
         }
         const unsigned long long t_s1 = stamp();
 
-        // (c) this step's transfers have landed (they had four tiles of time).  The wave reads back its own bound words right away (its
+        // (c) this step's transfers have landed (they had the step's tiles of time).  The wave reads back its own bound words right away (its
         // own vmcnt(0) covers them) so that the lgkmcnt(0) below also retires those reads before the next step's transfer can overwrite
         // the words; then the barrier publishes the chunk and the row ids to the other waves.
         __builtin_amdgcn_s_waitcnt(0x0f70);          // vmcnt(0)
@@ -686,7 +748,7 @@ __global__ __launch_bounds__(NW * 64, NB == 2 ? 2 : 1) void dense_prune_kernel(c
 
 // ------------------------------------------------------------------------------------------
 // Round 6: the same algorithm with ONE wave per SIMD.  Workgroup = 4 waves x 4 query tiles (the same 512 query pixels, the same grid, the same LDS ring
-// and DMA plan geometry as dense_prune_kernel<8, 0>); a wave holds both planes of FOUR query tiles (224 registers of the 512 a lone wave may have) and
+// and DMA plan geometry as the record-ring dense_prune_kernel<8, 0, 4, false>); a wave holds both planes of FOUR query tiles (224 registers of the 512 a lone wave may have) and
 // TWO accumulator sets, so that
 //   * every A fragment read from LDS feeds four MFMAs instead of two (half the LDS read traffic per product),
 //   * the A fragments of tile t + 1 are requested before tile t's 28 MFMAs are issued (a whole tile of cover for the LDS latency),
@@ -1081,6 +1143,14 @@ inline int split_tiles_per_chunk() {
     static const int nb = (AOC_DEV_ENV_INT("AOC_DENSE_NB", SP_NB) == 2 && split_waves() == 4) ? 2 : SP_NB;
     return nb;
 }
+inline int split_ckpt();
+inline bool split_hi_ring() {
+    // the product stages hi planes only, eight tiles per chunk (dense_prune_kernel<8, 0, 8, true>).  Developer switch AOC_DENSE_HI=0 (development
+    // build): the ring of whole records, four tiles per chunk -- the A / B partner of profiles/dense_hi_ring_ab.txt, and what the development
+    // variants (checkpoint, four waves, two-tile chunks) keep using
+    static const bool hi = AOC_DEV_ENV_INT("AOC_DENSE_HI", 1) != 0 && split_waves() == 8 && split_tiles_per_chunk() == SP_NB && split_ckpt() == 0;
+    return hi;
+}
 inline int split_nsplit(int64_t m) {
     const int64_t rpb = (int64_t)split_waves() * SP_NQ * 32;
     const int64_t row_blocks = (m + rpb - 1) / rpb;
@@ -1220,8 +1290,9 @@ int aoc_dense_match_min_split_cached(const float *query, const void *query_rec, 
     const int nw = split_waves();
     const int64_t rpb = (int64_t)nw * SP_NQ * 32;
     const dim3 grid((unsigned)((m + rpb - 1) / rpb), ns);
-    const int nb = split_tiles_per_chunk();
-    const size_t lds = sp_lds_bytes(nw, nb);
+    const bool hi = split_hi_ring();
+    const int nb = hi ? SP_NB_HI : split_tiles_per_chunk();
+    const size_t lds = sp_lds_bytes(nw, nb, hi);
 #if defined(AOC_DEV) || AOC_DENSE_Q4
     if (split_q4()) {
         // one wave per SIMD, four query tiles per wave (dense_prune_q4_kernel): same grid, same plan, same gbest
@@ -1244,24 +1315,25 @@ int aoc_dense_match_min_split_cached(const float *query, const void *query_rec, 
     static const int dbg = AOC_DEV_ENV_INT("AOC_DENSE_DEBUG", 0);       // developer switch: timing experiments only
     const int ckpt = split_ckpt();
     int launched = 0;
-#define AOC_DENSE_LAUNCH(NW_, CK_, NB_)                                                                                                                     \
-    if (!launched && nw == NW_ && ckpt == CK_ && nb == NB_) {                                                                                               \
-        static const bool lds_ok = hipFuncSetAttribute(reinterpret_cast<const void *>(dense_prune_kernel<NW_, CK_, NB_>),                                  \
+#define AOC_DENSE_LAUNCH(NW_, CK_, NB_, HI_)                                                                                                                  \
+    if (!launched && nw == NW_ && ckpt == CK_ && nb == NB_ && hi == HI_) {                                                                                        \
+        static const bool lds_ok = hipFuncSetAttribute(reinterpret_cast<const void *>(dense_prune_kernel<NW_, CK_, NB_, HI_>),                             \
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;                                \
         if (!lds_ok) return AOC_ERR_LAUNCH;                                                                                                                 \
         if (probe.start) (void)hipEventRecord(probe.start, st);                                                                                             \
-        hipLaunchKernelGGL((dense_prune_kernel<NW_, CK_, NB_>), grid, dim3(NW_ * 64), lds, st, static_cast<const uint4 *>(query_rec), query_sqnorm, m,           \
+        hipLaunchKernelGGL((dense_prune_kernel<NW_, CK_, NB_, HI_>), grid, dim3(NW_ * 64), lds, st, static_cast<const uint4 *>(query_rec), query_sqnorm, m,      \
                            static_cast<const uint4 *>(pool_rec), w.tile_rows, w.tile_obj, w.n_tiles, w.gate, w.pmax, n_obj, w.gbest, dbg,                   \
                            query_rec_tiled ? 1 : 0);                                                                                                        \
         launched = 1;                                                                                                                                       \
     }
-    AOC_DENSE_LAUNCH(8, 0, 4)
+    AOC_DENSE_LAUNCH(8, 0, 8, true)
 #ifdef AOC_DEV
-    AOC_DENSE_LAUNCH(8, 3, 4)
-    AOC_DENSE_LAUNCH(8, 4, 4)
-    AOC_DENSE_LAUNCH(4, 0, 4)
-    AOC_DENSE_LAUNCH(4, 3, 4)
-    AOC_DENSE_LAUNCH(4, 0, 2)
+    AOC_DENSE_LAUNCH(8, 0, 4, false)
+    AOC_DENSE_LAUNCH(8, 3, 4, false)
+    AOC_DENSE_LAUNCH(8, 4, 4, false)
+    AOC_DENSE_LAUNCH(4, 0, 4, false)
+    AOC_DENSE_LAUNCH(4, 3, 4, false)
+    AOC_DENSE_LAUNCH(4, 0, 2, false)
 #endif
 #undef AOC_DENSE_LAUNCH
     if (!launched) return AOC_ERR_UNSUPPORTED;

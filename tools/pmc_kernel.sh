@@ -1,5 +1,5 @@
 #!/bin/bash
-# Developer tool (GPU box): one rocprofv3 --pmc pass (counters only, with the kernel trace) over a command; prints the per-dispatch
+# Developer tool (GPU box): one rocprofv3 --pmc pass (counters only: no tracing option goes together with --pmc) over a command; prints the per-dispatch
 # averages of every collected counter for the kernels whose name contains <pattern>.
 # Usage: tools/pmc_kernel.sh <pattern> "<counters>" <command...>
 pat=$1; ctrs=$2; shift 2
@@ -9,7 +9,7 @@ for a in "$@"; do if [ -f "$a" ]; then a=$(realpath "$a"); fi; args+=("$a"); don
 set -- "${args[@]}"
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/pmc_k
-rocprofv3 --kernel-trace --pmc $ctrs -d /tmp/pmc_k -o pmc --output-format csv -- "$@" > /tmp/pmc_k.log 2>&1
+rocprofv3 --pmc $ctrs -d /tmp/pmc_k -o pmc --output-format csv -- "$@" > /tmp/pmc_k.log 2>&1
 python3 - "$pat" <<'PY'
 import csv, glob, collections, sys
 f = glob.glob("/tmp/pmc_k/**/*counter_collection.csv", recursive=True)
