@@ -580,6 +580,42 @@ int aoc_confident_labels(const float *probs, int n_ch, int64_t n, uint32_t exist
 int aoc_label_onehot_nearest(const int32_t *label, int H, int W, int h, int w, int n_obj, float *onehot_hwc,
                              aoc_stream_t stream);
 
+/* Test-time augmentation (--flip / --ms of tools/eval_net_mm_rpa.py:21-23 -> cfg.TEST_FLIP, cfg.TEST_MULTISCALE): the tail of one frame of
+ * eval_manager_mm.py:196-361 for a LIST of augmented samples as ONE launch.  Per output pixel (y, x), in the reference's order:
+ *   1. for each augmentation a, in order: p_a[c] = softmax_c(bilinear_{align_corners=True}(logits_a)[c]) (aocnet.py:103-106) taken at (y, x), or at
+ *      (y, W - 1 - x) when flip[a] (the planes are those of the horizontally mirrored image, :285-286); channels whose bit of exist_bits[a] is
+ *      clear become 0 AFTER the soft-max, without renormalisation (:253-265);
+ *   2. s[c] = sum_a p_a[c] in fp32, in augmentation order; label = first maximum of s (torch.argmax of the mean, :318-320), then the join_label
+ *      override of aoc_confident_labels (:321-326);
+ *   3. entropy -sum_{c seen} p log(p + 1e-6) (shannon_entropy.py:10-13), "seen" = exist_bits of the last augmentation:
+ *      mode 0 (reference): p = the LAST augmentation's probabilities at (y, x) in ITS OWN orientation, not flipped back -- all_pred_exist is built
+ *      before the flip of :286, and :306 / :339 read what the last loop iteration left;   mode 1 (consistent): p = s / n_aug.
+ *      Then the join_label terms and > unc_ratio -> 125 as in aoc_confident_labels (:339-346, :357-361);
+ *   4. outputs, each optional (NULL = not written; at least one): label, confident, label_flipped[y, x] = label[y, W - 1 - x] (:327-329),
+ *      confident_flipped (mode 1 only), entropy, mean_probs [n_ch, H, W] = s / n_aug.
+ * exist_bits is per augmentation because the reference updates label_all_list INSIDE its augmentation loop (:268-272): on a frame whose ground
+ * truth introduces an object, augmentation 0 still zeroes that channel and the later ones do not.  Every other caller passes n_aug equal values.
+ * With n_aug = 1 and no flip the call is interpolate -> softmax -> aoc_confident_labels in one launch.  n_aug <= AOC_MAX_TTA_AUGS (eight scales
+ * with their flipped twins), n_ch <= 32 (beyond: AOC_ERR_UNSUPPORTED); everything is validated before the launch. */
+#define AOC_MAX_TTA_AUGS 16
+typedef struct aoc_tta_desc {
+    int32_t n_aug, n_ch;             /* augmentations, channels (objects incl. background) */
+    int32_t H, W;                    /* output (image) size */
+    int32_t mode;                    /* 0 = reference, 1 = consistent (see 3.) */
+    float unc_ratio;
+    int32_t h[AOC_MAX_TTA_AUGS], w[AOC_MAX_TTA_AUGS];    /* size of augmentation a's logit planes */
+    int32_t flip[AOC_MAX_TTA_AUGS];                      /* 0 / 1 */
+    uint32_t exist_bits[AOC_MAX_TTA_AUGS];               /* bit c = label c has appeared in a ground-truth map (aoc_confident_labels) */
+    float scale_h[AOC_MAX_TTA_AUGS], scale_w[AOC_MAX_TTA_AUGS];   /* set by the call ((h - 1) / (H - 1), ...): the caller's values are ignored */
+    int64_t plane_stride[AOC_MAX_TTA_AUGS];              /* floats between two channels' planes, >= h * w */
+    const float *logits[AOC_MAX_TTA_AUGS];               /* [n_ch] planes of [h, w] float32, row-major */
+    const int32_t *join_label;       /* [H, W] or NULL (aoc_confident_labels) */
+    int32_t *label, *confident, *label_flipped, *confident_flipped;   /* [H, W] each, or NULL */
+    float *entropy;                  /* [H, W] or NULL */
+    float *mean_probs;               /* [n_ch, H, W] or NULL */
+} aoc_tta_desc;
+int aoc_tta_merge(const aoc_tta_desc *desc, aoc_stream_t stream);
+
 /* J (region similarity) and F (boundary measure) of a predicted label map against the ground truth, summed over the foreground
  * objects 1 .. n_obj-1 and ACCUMULATED on the device: accum[0] += sum_o J_o, accum[1] += sum_o F_o,
  * accum[2] += n_obj - 1, accum[3] += 1.  The reference scores saved PNGs with the external DAVIS toolkit (README.md:110; its only

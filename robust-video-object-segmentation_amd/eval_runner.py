@@ -83,9 +83,16 @@ class HotPathBackend:
     """One frame on the MI355X: matching (libaoc_hip.so) -> DynamicPreHead -> stand-in read-out -> soft-max.  The conv decoder is out of
     scope; its stand-in ranks the objects by their matching evidence (logit = -12 x the mean of the dense-matching and the widest
     local-window proto-mask channels, i.e. nearest-neighbour label propagation) plus a small seeded linear read-out of the pre-head output,
-    which is computed because the real decoder consumes it.  Seeded, so every rank decodes identically."""
+    which is computed because the real decoder consumes it.  Seeded, so every rank decodes identically.
 
-    def __init__(self, device, dense_precision=None, ahead=True, lane=0):
+    augmentations = [(h_a, w_a, flip), ...] (eval_loop.multi_restrict_sizes through map_size): test-time augmentation.  Every augmentation is a
+    full single-augmentation lane of the above -- a HotPathBackend of its own at map size (h_a, w_a): resident pool, FrameRunner workspace,
+    ahead-of-time k-means chains, RandomState seeded spec.seed + 7919 a (the reference draws from numpy's unseeded global stream: there is no
+    stream to reproduce across augmentations, only the per-call contract) -- behind ONE eval_loop.AugmentedMemoryPolicy.  The stand-in for "the
+    backbone on the resized / mirrored image" is ops.resize_bilinear_hwc of the embedding and a flip along w; the lanes' low-resolution logits
+    are decided by one aoc_tta_merge per frame.  None (the default) is the single-augmentation path, unchanged."""
+
+    def __init__(self, device, dense_precision=None, ahead=True, lane=0, augmentations=None, tta_mode="reference"):
         from . import hotpath
         self.hot = hotpath
         self.device = device
@@ -99,6 +106,9 @@ class HotPathBackend:
         self.side = None
         self.lane = int(lane)                  # which of the rank's lanes this backend serves (its side stream is kept per lane)
         self._worker, self._pending = None, None
+        self.augmentations = None if augmentations is None else [(int(h), int(w), bool(f)) for h, w, f in augmentations]
+        self.tta_mode = tta_mode
+        self.tta, self._lanes = None, None
 
     def _head(self, n_ch):
         if n_ch not in self._heads:
@@ -112,8 +122,17 @@ class HotPathBackend:
         return self._heads[n_ch]
 
     def start(self, spec):
-        from .eval_loop import MemoryPolicy
+        from .eval_loop import AugmentedMemoryPolicy, MemoryPolicy
         self.spec = spec
+        if self.augmentations is not None:
+            import dataclasses
+            if self._lanes is None:
+                self._lanes = [HotPathBackend(self.device, self.dense_precision, self.ahead, lane=self.lane) for _ in self.augmentations]
+            self.tta = AugmentedMemoryPolicy(len(self.augmentations), [f for _, _, f in self.augmentations], spec.mem_every, 1.0, mode=self.tta_mode)
+            for a, (h, w, _) in enumerate(self.augmentations):
+                self._lanes[a].start(dataclasses.replace(spec, h=h, w=w, seed=spec.seed + 7919 * a))
+                self._lanes[a].policy = self.tta.lane(a)            # the lane reads ITS lists of the shared policy
+            return
         self.mc = self.hot.MatchingConfig(CLUSTER_LEVELS=list(spec.levels) if len(spec.levels) > 1 else None, CLUSTER_NUM=spec.levels[0],
                                           MEM_EVERY=spec.mem_every)
         self.policy = MemoryPolicy(mem_every=spec.mem_every, unc_ratio=1.0)
@@ -146,7 +165,16 @@ class HotPathBackend:
             self.side = _cached_stream(self.device, "side", self.lane, priority=SIDE_STREAM_PRIORITY)
 
     def first_frame(self, emb, gt_label):
+        if self.augmentations is not None:
+            self.tta.start([self._lane_emb(a, emb) for a in range(len(self.augmentations))], gt_label)
+            return
         self.policy.start(emb, gt_label)
+
+    def _lane_emb(self, a, emb):
+        """The embedding augmentation a's backbone would produce: resized to its map, mirrored along w for a flipped one."""
+        h, w, flip = self.augmentations[a]
+        e = emb if tuple(emb.shape[:2]) == (h, w) else ops.resize_bilinear_hwc(emb, h, w)
+        return e.flip(1).contiguous() if flip else e
 
     def _reference_pool(self):
         """policy.reference_pool() without re-stacking: the frames that joined the pool since the last call are appended in place."""
@@ -236,6 +264,19 @@ class HotPathBackend:
     @torch.no_grad()
     def frame(self, emb):
         """emb [h, w, C] -> predicted label map [H, W] int32 (H = 4 h: the reference's masks live at image resolution)."""
+        if self.augmentations is not None:
+            embs = [self._lane_emb(a, emb) for a in range(len(self.augmentations))]
+            logits = [lane._lane_logits(e) for lane, e in zip(self._lanes, embs)]
+            return self.tta.update(embs, logits)[0]                 # ONE aoc_tta_merge: bilinear + soft-max + flip-back + mean + decision
+        h, w = self.spec.h, self.spec.w
+        logit = self._lane_logits(emb)
+        logit = torch.nn.functional.interpolate(logit[None], size=(4 * h, 4 * w), mode="bilinear", align_corners=True)[0]
+        label, _, _ = self.policy.update(emb, torch.softmax(logit, dim=0))
+        return label
+
+    @torch.no_grad()
+    def _lane_logits(self, emb):
+        """One lane up to the decoder stand-in's low-resolution logits [n_obj, h, w]."""
         spec, h, w = self.spec, self.spec.h, self.spec.w
         ref_emb, ref_lab, prev_emb, prev_lab, changed = self._reference_pool()
         if not changed:
@@ -253,10 +294,7 @@ class HotPathBackend:
         pre, wv = self._head(feat.shape[1])
         y = pre(feat)                                                          # [O, 64, h, w]
         ch = self.hot.channel_slices(self.mc)
-        logit = -12.0 * 0.5 * (feat[:, ch["global_fg"]] + feat[:, ch["local"]]) + torch.einsum("ochw,c->ohw", y, wv)
-        logit = torch.nn.functional.interpolate(logit[None], size=(4 * h, 4 * w), mode="bilinear", align_corners=True)[0]
-        label, _, _ = self.policy.update(emb, torch.softmax(logit, dim=0))
-        return label
+        return -12.0 * 0.5 * (feat[:, ch["global_fg"]] + feat[:, ch["local"]]) + torch.einsum("ochw,c->ohw", y, wv)
 
 
 def _gt_fullres(lab_hw):

@@ -969,6 +969,64 @@ def label_onehot_nearest(label_hw, h, w, n_obj):
     return out
 
 
+MAX_TTA_AUGS = 16
+
+
+class _TtaDesc(ctypes.Structure):
+    """aoc_tta_desc of include/aoc_hip.h."""
+    _fields_ = [("n_aug", ctypes.c_int32), ("n_ch", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("mode", ctypes.c_int32),
+                ("unc_ratio", ctypes.c_float),
+                ("h", ctypes.c_int32 * MAX_TTA_AUGS), ("w", ctypes.c_int32 * MAX_TTA_AUGS), ("flip", ctypes.c_int32 * MAX_TTA_AUGS),
+                ("exist_bits", ctypes.c_uint32 * MAX_TTA_AUGS), ("scale_h", ctypes.c_float * MAX_TTA_AUGS), ("scale_w", ctypes.c_float * MAX_TTA_AUGS),
+                ("plane_stride", ctypes.c_int64 * MAX_TTA_AUGS), ("logits", ctypes.c_void_p * MAX_TTA_AUGS),
+                ("join_label", ctypes.c_void_p),
+                ("label", ctypes.c_void_p), ("confident", ctypes.c_void_p), ("label_flipped", ctypes.c_void_p), ("confident_flipped", ctypes.c_void_p),
+                ("entropy", ctypes.c_void_p), ("mean_probs", ctypes.c_void_p)]
+
+
+TTA_MODES = {"reference": 0, "consistent": 1}
+
+
+def tta_merge(logits_list, flips, H, W, exist_bits, join_label=None, unc_ratio=1.0, mode="reference", want_mean=False):
+    """aoc_tta_merge: the per-augmentation decoder logits of one frame ([n_ch, h_a, w_a] each, those of flipped augmentations in the
+    mirrored image's orientation) -> dict(label, confident, label_flipped, entropy [H, W]; + confident_flipped in mode "consistent";
+    + mean_probs [n_ch, H, W] with want_mean) in ONE launch.  exist_bits: an int, or one int per augmentation (see include/aoc_hip.h)."""
+    logits_list = [_f32c(l) for l in logits_list]
+    _need_gpu(*logits_list, join_label)
+    A = len(logits_list)
+    if not 1 <= A <= MAX_TTA_AUGS:
+        raise ValueError(f"tta_merge: 1 .. {MAX_TTA_AUGS} augmentations, got {A}")
+    if len(flips) != A:
+        raise ValueError("tta_merge: one flip flag per augmentation")
+    bits = [exist_bits] * A if isinstance(exist_bits, int) else list(exist_bits)
+    if len(bits) != A:
+        raise ValueError("tta_merge: exist_bits is one value, or one per augmentation")
+    n_ch = logits_list[0].shape[0]
+    dev = logits_list[0].device
+    H, W = int(H), int(W)
+    d = _TtaDesc()
+    d.n_aug, d.n_ch, d.H, d.W, d.mode, d.unc_ratio = A, n_ch, H, W, TTA_MODES[mode], float(unc_ratio)
+    for a, l in enumerate(logits_list):
+        if l.dim() != 3 or l.shape[0] != n_ch:
+            raise ValueError("tta_merge: every augmentation is [n_ch, h, w] with the same n_ch")
+        d.h[a], d.w[a], d.flip[a], d.exist_bits[a] = l.shape[1], l.shape[2], int(bool(flips[a])), int(bits[a]) & 0xFFFFFFFF
+        d.plane_stride[a], d.logits[a] = l.shape[1] * l.shape[2], l.data_ptr()
+    if join_label is not None:
+        join_label = join_label.to(torch.int32).contiguous()
+        assert join_label.shape == (H, W)
+        d.join_label = join_label.data_ptr()
+    out = {k: torch.empty(H, W, dtype=torch.int32, device=dev) for k in ("label", "confident", "label_flipped")}
+    if d.mode == 1:
+        out["confident_flipped"] = torch.empty(H, W, dtype=torch.int32, device=dev)
+    out["entropy"] = torch.empty(H, W, dtype=torch.float32, device=dev)
+    if want_mean:
+        out["mean_probs"] = torch.empty(n_ch, H, W, dtype=torch.float32, device=dev)
+    for k, t in out.items():
+        setattr(d, k, t.data_ptr())
+    _lib.check(_lib.lib().aoc_tta_merge(ctypes.byref(d), _stream()), "aoc_tta_merge")
+    return out
+
+
 class MaskJF:
     """Device-side accumulator of the DAVIS region similarity J and boundary measure F (aoc_mask_jf_accumulate): add(pred, gt) enqueues
     three small kernels and never synchronises; totals() reads the four float64 accumulators back once."""
