@@ -1116,6 +1116,11 @@ def cond_codes(gap, plane_means, head, w1, b1, w2, b2, w3, b3):
     _need_gpu(gap, plane_means, head, w1, w2, w3)
     N, C = gap.shape
     D = head.shape[1]
+    # the library reads W1, W2 as [C, C] and W3 as [D, D] from bare pointers: a smaller tensor would be read past its end
+    want = ((N, C), (N, D), (C, C), (C,), (C, C), (C,), (D, D), (D,))
+    have = tuple(tuple(t.shape) for t in (plane_means, head, w1, b1, w2, b2, w3, b3))
+    if have != want:
+        raise _lib.AocHipError(f"aoc_cond_codes: plane_means, head, w1, b1, w2, b2, w3, b3 must have shapes {want}, got {have}")
     code = torch.empty(N, 2 * C + D, dtype=torch.float32, device=gap.device)
     _lib.check(_lib.lib().aoc_cond_codes(_p(gap), _p(plane_means), _p(head), _p(_f32c(w1)), _p(_f32c(b1)), _p(_f32c(w2)), _p(_f32c(b2)), _p(_f32c(w3)),
                                          _p(_f32c(b3)), N, C, D, _p(code), _stream()), "aoc_cond_codes")

@@ -111,6 +111,7 @@ def test_entropy_kernel_vs_reference_golden(aoc):
 
 @pytest.mark.parametrize("mode,after_relu", [("l2", False), ("l1", False), ("l1", True)])
 def test_gct_vs_oracle(aoc, mode, after_relu):
+    """gct.GCT end to end, a fitted tolerance.  The kernels on their own, against float64 under derived bounds: test_gpu_decoder_kernels.py."""
     from oracle import calibration as ocal
     rng = np.random.RandomState(3)
     N, C, H, W = 3, 48, 31, 45
@@ -128,6 +129,7 @@ def test_gct_vs_oracle(aoc, mode, after_relu):
 
 
 def test_ia_logit_vs_oracle(aoc):
+    """gct.IA_logit end to end, a fitted tolerance.  The kernels on their own, against float64 under derived bounds: test_gpu_decoder_kernels.py."""
     from oracle import calibration as ocal
     rng = np.random.RandomState(4)
     N, C, H, W, D = 4, 37, 29, 41, 400
@@ -145,7 +147,7 @@ def test_ia_logit_vs_oracle(aoc):
 @pytest.mark.parametrize("O,h,w", [(4, 121, 213), (3, 17, 23)])
 def test_dynamic_prehead_vs_torch(aoc, O, h, w):
     """hotpath.DynamicPreHead against the same torch modules the reference class is made of (decoding_module.py:228-240),
-    and the fused concatenation of aocnet.py:362."""
+    and the fused concatenation of aocnet.py:362 (a fitted tolerance).  The kernels on their own, against float64 under derived bounds: test_gpu_decoder_kernels.py."""
     rng = np.random.RandomState(O)
     x = torch.from_numpy(rng.uniform(-1, 1, (O, 24, h, w)).astype(np.float32))
     emb = torch.from_numpy((np.maximum(rng.randn(h, w, 100), 0) * 0.3).astype(np.float32))

@@ -457,7 +457,7 @@ def test_incremental_proxies_accuracy(aoc):
 
 def test_bottleneck_golden(aoc, golden):
     """The decoder's residual block (gct.py:38-90) with the GCT gate and the GroupNorm + ReLU (+ residual) streams on the HIP library,
-    against the output of the reference class."""
+    against the output of the reference class (fitted tolerances).  The kernels on their own, against float64 under derived bounds: test_gpu_decoder_kernels.py."""
     g = golden("bottleneck_64_128")
     blk = aoc.gct.Bottleneck(64, 128).cuda()
     sd = {k[2:].replace("__", "."): torch.from_numpy(v) for k, v in g.items() if k.startswith("p_")}
@@ -479,7 +479,8 @@ def test_bottleneck_golden(aoc, golden):
 
 
 def test_head_delta_equals_torch(aoc):
-    """aoc_head_delta = torch.cat([head, px.sum(0, keepdim=True) - px], 1) (decoding_module.py:126-130)."""
+    """aoc_head_delta = torch.cat([head, px.sum(0, keepdim=True) - px], 1) (decoding_module.py:126-130), a fitted tolerance.
+    The kernels on their own, against float64 under derived bounds: test_gpu_decoder_kernels.py."""
     g = torch.Generator().manual_seed(5)
     for n_obj, D, C in [(4, 400, 512), (1, 400, 320), (9, 912, 128)]:
         head, px = torch.randn(n_obj, D, generator=g), torch.randn(n_obj, C, generator=g)
@@ -520,7 +521,8 @@ def test_local_register_kernel_vs_oracle(aoc, C, h, w, mld, rate, down):
 
 @pytest.mark.parametrize("hw", [1, 3, 7, 1021, 121 * 213, 61 * 107])
 def test_plane_mean_every_alignment(aoc, hw):
-    """aoc_plane_mean with plane sizes that put the planes at every 4-byte phase of a 16-byte line (scalar head, 16-byte body, scalar tail)."""
+    """aoc_plane_mean with plane sizes that put the planes at every 4-byte phase of a 16-byte line (scalar head, 16-byte body, scalar tail);
+    a fitted tolerance.  The kernels on their own, against float64 under derived bounds: test_gpu_decoder_kernels.py."""
     g = torch.Generator().manual_seed(hw)
     x = torch.randn(3, 5, hw, 1, generator=g)
     got = aoc.ops.plane_mean(x.cuda()).cpu()

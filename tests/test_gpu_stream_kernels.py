@@ -14,13 +14,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from float64_bounds import U, _check_bound, gamma
+
 pytestmark = pytest.mark.gpu
-
-U = 2.0 ** -24
-
-
-def gamma(n):
-    return n * U / (1.0 - n * U)
 
 
 @pytest.fixture(scope="module")
@@ -38,16 +34,6 @@ def dev(a):
 
 def host(t):
     return t.detach().cpu()
-
-
-def _check_bound(got, want, tol, slip, what):
-    """got within tol of the float64 reference `want`; the slipped reference must leave the bound somewhere."""
-    got, want, slip = (torch.as_tensor(v).double() for v in (got, want, slip))
-    tol = torch.as_tensor(tol, dtype=torch.float64)
-    err = (got - want).abs()
-    bad = ~(err <= tol)
-    assert not bad.any(), f"{what}: {int(bad.sum())} elements outside the bound, worst excess {float((err - tol).max()):.3e}"
-    assert ((slip - want).abs() > tol).any(), f"{what}: the slipped reference stays inside the bound (bound too loose)"
 
 
 # ------------------------------------------------------------------------------------------ 1. J / F metric
