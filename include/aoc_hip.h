@@ -554,6 +554,41 @@ int aoc_gct_gate(const float *plane_sums, const float *alpha, const float *gamma
 int aoc_object_logit(const float *x, int N, int C, int64_t hw, const float *weight, int64_t weight_stride,
                      const float *bias, int64_t bias_stride, float *out, aoc_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The decoder's tail (csrc/decoder_tail.hip): the shortcut stage of decoder_final and the prediction head.  fp32, up to AOC_MAX_OBJECTS
+ * objects (beyond: AOC_ERR_UNSUPPORTED); every argument is validated before the first launch (no device needed for a rejection).
+ *
+ * Bicubic resize = PyTorch's upsample_bicubic2d with align_corners=True (decoding_module.py:163): A = -0.75, four taps per axis at
+ * floor(src) - 1 .. + 2 clamped to the map, src = o (in - 1) / (out - 1) (0 when out = 1).  The coordinate is split in integers
+ * (tap index o (in - 1) div (out - 1), exact; fraction float(o (in - 1) mod (out - 1)) / float(out - 1), one rounding).
+ *
+ * Mean over the H x W map of the bicubic upsample of each coarse plane in [P, h, w], computed from the coarse plane alone
+ * (decoding_module.py:163 + :172 for the upsampled channels): (1 / HW) sum_ij cy[i] cx[j] x[i, j], cy / cx = column sums of the two 1-D
+ * interpolation matrices.  out [P]. */
+int aoc_bicubic_plane_mean(const float *in, int64_t P, int h, int w, int H, int W, float *out, aoc_stream_t stream);
+/* decoding_module.py:163 + :170 (+ the scaling of ATT:15-16) without the intermediate tensors: out [N, Ce + Cr, H, W] with
+ *   out[n, c < Ce] = gain[n, c] * bicubic(x[n, c]),  out[n, Ce + c] = gain[n, Ce + c] * low[n, c];
+ * x [N, Ce, h, w]; low [N, Cr, H, W] (NULL with Cr = 0: a plain plane resize); gain [N, Ce + Cr] or NULL (= 1). */
+int aoc_bicubic_cat_scale(const float *x, const float *low, const float *gain, int N, int Ce, int Cr, int h, int w, int H, int W,
+                          float *out, aoc_stream_t stream);
+/* decoding_module.py:163 and :170-176 as one call without host synchronisation: plane means of the concatenation (the upsampled part from the
+ * coarse map, the shortcut part low -- the branch after its ReLU, :168 -- through the plane-mean kernel), px1_delta appended to IA_head
+ * [N, head_dim] (:173-176), IA10's gain (weight [Ce + Cr, head_dim + Ce + Cr], bias [Ce + Cr] or NULL; ATT:13-14) and the gated
+ * concatenation out [N, Ce + Cr, H, W].  Optional outputs (NULL = not wanted): plane_means [N, Ce + Cr], gain [N, Ce + Cr]. */
+size_t aoc_shortcut_stage_workspace_bytes(int N, int Ce, int Cr, int head_dim);
+int aoc_shortcut_stage_enqueue(const float *x, const float *low, const float *IA_head, const float *weight, const float *bias, int N,
+                               int Ce, int Cr, int head_dim, int h, int w, int H, int W, float *out, float *plane_means, float *gain,
+                               void *workspace, size_t workspace_bytes, aoc_stream_t stream);
+/* decoding_module.py:144-147 in one launch: IA_logit (:151-160) for the fg and bg heads and augment_background_logit (:213-225).
+ * wb_fg, wb_bg: rows of [C weights | bias] per object, `stride` floats apart (the two IA_final outputs [N, C + 1]); x [N, C, hw] is read once.
+ *   pred[n] = fg[n];  for N > 1: pred[0] += min over n >= 1 of bg[n]   (bg[0] is not computed; wb_bg may be NULL for N = 1)
+ * pred [N, hw] is the reference's [1, N, h, w] (the permute of :224).  fg and bg are bit-equal to what the object-logit call gives. */
+int aoc_logit_head(const float *x, const float *wb_fg, const float *wb_bg, int64_t stride, int N, int C, int64_t hw, float *pred,
+                   aoc_stream_t stream);
+/* augment_background_logit alone (decoding_module.py:213-225) for logits that already exist: fg, bg [N, hw] -> pred [N, hw] as above
+ * (bg may be NULL for N = 1; pred may alias fg). */
+int aoc_background_merge(const float *fg, const float *bg, int N, int64_t hw, float *pred, aoc_stream_t stream);
+
 /* GroupNorm (+ residual) + ReLU of the decoder's Bottleneck (networks/layers/gct.py:69-90: bn1/bn2 followed by relu, bn3 followed by
  * `out += residual; relu`): y = [relu]( GroupNorm_groups(x) * gamma + beta [+ residual] ), x [N, C, hw], biased variance over each
  * group's channels x hw as torch.nn.GroupNorm.  Two streams over x (statistics, apply) and one write instead of the separate

@@ -106,6 +106,12 @@ SIGNATURES = {
     "aoc_label_mix": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp]),
     "aoc_plane_mean": (_i, [_vp, _i64, _i64, _vp, _vp]),
     "aoc_head_delta": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp]),
+    "aoc_bicubic_plane_mean": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _vp]),
+    "aoc_bicubic_cat_scale": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "aoc_shortcut_stage_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "aoc_shortcut_stage_enqueue": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "aoc_logit_head": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i64, _vp, _vp]),
+    "aoc_background_merge": (_i, [_vp, _vp, _i, _i64, _vp, _vp]),
 }
 
 STATUS = {0: "AOC_OK", -1: "AOC_ERR_INVALID_ARG", -2: "AOC_ERR_WORKSPACE", -3: "AOC_ERR_LAUNCH", -4: "AOC_ERR_UNSUPPORTED"}

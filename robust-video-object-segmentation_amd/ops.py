@@ -1110,6 +1110,85 @@ def object_logit(x, weight_bias):
     return out
 
 
+# ------------------------------------------------------------------------------------------ the decoder's tail (csrc/decoder_tail.hip)
+def bicubic_plane_mean(x, size):
+    """x [N, C, h, w] -> [N, C]: the mean over the map of F.interpolate(x, size, mode='bicubic', align_corners=True), from x alone."""
+    x = _f32c(x)
+    _need_gpu(x)
+    N, C, h, w = x.shape
+    H, W = (int(v) for v in size)
+    out = torch.empty(N, C, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().aoc_bicubic_plane_mean(_p(x), N * C, h, w, H, W, _p(out), _stream()), "aoc_bicubic_plane_mean")
+    return out
+
+
+def bicubic_cat_scale(x, low=None, gain=None, size=None, out=None):
+    """gain[:, :, None, None] * torch.cat([F.interpolate(x, size, mode='bicubic', align_corners=True), low], 1) in one call
+    (decoding_module.py:163, :170 and the scaling of ATT:15-16).  x [N, Ce, h, w]; low [N, Cr, H, W] or None (size gives H, W then);
+    gain [N, Ce + Cr] or None (= 1)."""
+    x = _f32c(x)
+    low = _f32c(low) if low is not None else None
+    gain = _f32c(gain) if gain is not None else None
+    _need_gpu(x, low, gain)
+    N, Ce, h, w = x.shape
+    Cr = low.shape[1] if low is not None else 0
+    H, W = (int(v) for v in (low.shape[2:] if size is None else size))
+    if low is not None and tuple(low.shape) != (N, Cr, H, W):
+        raise _lib.AocHipError(f"aoc_bicubic_cat_scale: low must be [{N}, Cr, {H}, {W}], got {tuple(low.shape)}")
+    if gain is not None and tuple(gain.shape) != (N, Ce + Cr):
+        raise _lib.AocHipError(f"aoc_bicubic_cat_scale: gain must be [{N}, {Ce + Cr}], got {tuple(gain.shape)}")
+    y = torch.empty(N, Ce + Cr, H, W, dtype=torch.float32, device=x.device) if out is None else out
+    _lib.check(_lib.lib().aoc_bicubic_cat_scale(_p(x), _p(low), _p(gain), N, Ce, Cr, h, w, H, W, _p(y), _stream()), "aoc_bicubic_cat_scale")
+    return y
+
+
+def shortcut_stage(x, low, IA_head, weight, bias, want_debug=False, out=None):
+    """decoding_module.py:163 and :170-176 in one C call: IA10(cat([bicubic(x), low], 1), cat([IA_head, px1_delta], 1)) with IA10's
+    Linear given as weight [Ce + Cr, D + Ce + Cr], bias.  x [N, Ce, h, w], low [N, Cr, H, W] (the shortcut branch after its ReLU),
+    IA_head [N, D].  want_debug: also the plane means and the gain, both [N, Ce + Cr]."""
+    x, low, IA_head, weight = _f32c(x), _f32c(low), _f32c(IA_head), _f32c(weight)
+    bias = _f32c(bias) if bias is not None else None
+    _need_gpu(x, low, IA_head, weight, bias)
+    N, Ce, h, w = x.shape
+    Cr, H, W = low.shape[1:]
+    D = IA_head.shape[1]
+    want = ((N, Cr, H, W), (N, D), (Ce + Cr, D + Ce + Cr))
+    have = tuple(tuple(t.shape) for t in (low, IA_head, weight))
+    if have != want or (bias is not None and tuple(bias.shape) != (Ce + Cr,)):
+        raise _lib.AocHipError(f"aoc_shortcut_stage_enqueue: low, IA_head, weight must have shapes {want} and bias [{Ce + Cr}], got {have}")
+    L = _lib.lib()
+    y = torch.empty(N, Ce + Cr, H, W, dtype=torch.float32, device=x.device) if out is None else out
+    pm = torch.empty(N, Ce + Cr, dtype=torch.float32, device=x.device) if want_debug else None
+    gain = torch.empty(N, Ce + Cr, dtype=torch.float32, device=x.device) if want_debug else None
+    ws = _ws(L.aoc_shortcut_stage_workspace_bytes(N, Ce, Cr, D), x.device)
+    _lib.check(L.aoc_shortcut_stage_enqueue(_p(x), _p(low), _p(IA_head), _p(weight), _p(bias), N, Ce, Cr, D, h, w, H, W, _p(y), _p(pm), _p(gain),
+                                            _p(ws), ws.numel(), _stream()), "aoc_shortcut_stage_enqueue")
+    return (y, pm, gain) if want_debug else y
+
+
+def logit_head(x, wb_fg, wb_bg):
+    """decoding_module.py:144-147 in one launch.  x [N, C, H, W]; wb_fg, wb_bg [N, C + 1] (the two IA_final outputs: weights then bias)
+    -> pred [1, N, H, W] = fg logits, object 0's plus the min over the other objects' bg logits."""
+    x, wb_fg, wb_bg = _f32c(x), _f32c(wb_fg), _f32c(wb_bg)
+    _need_gpu(x, wb_fg, wb_bg)
+    N, C, H, W = x.shape
+    assert wb_fg.shape == (N, C + 1) and wb_bg.shape == (N, C + 1)
+    pred = torch.empty(1, N, H, W, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().aoc_logit_head(_p(x), _p(wb_fg), _p(wb_bg), C + 1, N, C, H * W, _p(pred), _stream()), "aoc_logit_head")
+    return pred
+
+
+def background_merge(fg_logit, bg_logit):
+    """augment_background_logit (decoding_module.py:213-225): fg_logit, bg_logit [N, 1, H, W] -> pred [1, N, H, W]."""
+    fg, bg = _f32c(fg_logit), _f32c(bg_logit)
+    _need_gpu(fg, bg)
+    N, _, H, W = fg.shape
+    assert fg.shape[1] == 1 and bg.shape == fg.shape
+    pred = torch.empty(1, N, H, W, dtype=torch.float32, device=fg.device)
+    _lib.check(_lib.lib().aoc_background_merge(_p(fg), _p(bg), N, H * W, _p(pred), _stream()), "aoc_background_merge")
+    return pred
+
+
 def cond_codes(gap, plane_means, head, w1, b1, w2, b2, w3, b3):
     """aoc_cond_codes: the three conditioning codes of CLB:68-80 concatenated -> [N, 2C + D]."""
     gap, plane_means, head = _f32c(gap), _f32c(plane_means), _f32c(head)
