@@ -599,6 +599,28 @@ int aoc_groupnorm_relu(const float *x, int N, int C, int64_t hw, int groups, con
                        size_t workspace_bytes, aoc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The decoder's memory modulators, decoding_module.py:192-210 (Modulator_1 / Modulator_2): the concatenation with the memory fused into
+ * gate 1, and gates 2 and 3 fused into the apply pass of the GroupNorm in front of them.  fp32.  The gain of both entry points is the
+ * routine of aoc_film_scale (same summation order), so each returns exactly the bits of the composition it replaces.  Every argument is
+ * validated before the first launch (no device needed for a rejection).
+ *
+ * torch.cat([x, mem], dim=1) (:193 / :203) + IA_gate (:194 / :204, ATT:12-17) in one launch; the concatenation is never written ungated:
+ *   y[o, c < Cx] = g[o, c] * x[o, c],  y[o, Cx + c] = g[o, Cx + c] * mem[o, c],  g = 1 + tanh(head W^T + b) over the Cx + Cm channels.
+ * x [n_obj, Cx, hw]; mem [n_obj, Cm, hw] (may alias x: the first frame of a sequence; NULL with Cm = 0, which is aoc_film_scale);
+ * head [n_obj, head_dim]; weight [Cx + Cm, head_dim]; bias [Cx + Cm] or NULL; y [n_obj, Cx + Cm, hw].  Every source plane is read once and
+ * y is written once, 16 bytes per lane whatever the 16-byte misalignments of the three base pointers are. */
+int aoc_cat_film_scale(const float *x, const float *mem, const float *head, const float *weight, const float *bias, int n_obj,
+                       int head_dim, int Cx, int Cm, int64_t hw, float *y, aoc_stream_t stream);
+/* aoc_groupnorm_relu followed by IA_gate (gct.py:84-90 + decoding_module.py:196,198 / :206,208) with the gate folded into the apply pass:
+ *   y = g[n, c] * [relu]( GroupNorm_groups(x) * gamma + beta [+ residual] ),  g = 1 + tanh(head W^T + b);
+ * head [N, head_dim]; weight [C, head_dim]; gate_bias [C] or NULL; everything else, the statistics pass and the workspace
+ * (aoc_groupnorm_relu_workspace_bytes) as aoc_groupnorm_relu.  y may alias x. */
+int aoc_groupnorm_relu_scale(const float *x, int N, int C, int64_t hw, int groups, const float *gamma, const float *beta,
+                             float eps, const float *residual, int relu, const float *head, const float *weight,
+                             const float *gate_bias, int head_dim, float *y, void *workspace, size_t workspace_bytes,
+                             aoc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Eval-loop memory policy (the caller of the matching path).
  *
  * aoc_confident_labels: the per-pixel decision of one frame, eval_manager_mm.py:253-265,300-326,339-346,357-361 with

@@ -34,5 +34,7 @@ from . import eval_loop  # noqa: F401,E402
 from . import gct  # noqa: F401,E402
 from . import eval_runner  # noqa: F401,E402
 from . import decoder_tail  # noqa: F401,E402
+from . import decoder_memory  # noqa: F401,E402
 
-__all__ = ["synthetic", "ops", "matching", "attention", "conditioning_layer", "hotpath", "sharding", "eval_loop", "gct", "eval_runner", "decoder_tail"]
+__all__ = ["synthetic", "ops", "matching", "attention", "conditioning_layer", "hotpath", "sharding", "eval_loop", "gct", "eval_runner", "decoder_tail",
+           "decoder_memory"]

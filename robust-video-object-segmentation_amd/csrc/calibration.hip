@@ -324,6 +324,30 @@ __global__ __launch_bounds__(256) void channel_scale_kernel(const float *__restr
     }
 }
 
+// The gain of one plane, 1 + tanh(h . w + bias[c]), by a workgroup of 256 threads (wsum: four floats of LDS; holds a barrier).  Every kernel
+// that gates a plane calls THIS routine, so the fused entry points return the bits of aoc_film_scale: the order of the sum is part of the
+// result.  Four strides of the dot product at a time, branch-free (clamped index, select afterwards): the eight loads are in flight together
+// instead of one dependent round trip per stride, which is most of a workgroup's life when its slice of the plane is small.
+__device__ __forceinline__ float film_gain_wg256(const float *__restrict__ h, const float *__restrict__ w, const float *__restrict__ bias, int c, int D,
+                                                 float *wsum) {
+    float acc = 0.0f;
+    for (int d0 = threadIdx.x; d0 < D; d0 += 4 * 256) {
+        float wv[4], hv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int d = min(d0 + u * 256, D - 1);
+            wv[u] = w[d];
+            hv[u] = h[d];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc += (d0 + u * 256 < D) ? wv[u] * hv[u] : 0.0f;
+    }
+    acc = aoc_wave_sum(acc);
+    if (aoc_lane() == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    return 1.0f + tanhf((wsum[0] + wsum[1] + wsum[2] + wsum[3]) + (bias ? bias[c] : 0.0f));
+}
+
 #ifdef AOC_DEV
 // FiLM gate in one launch: every block first computes its plane's gain 1 + tanh(head[o,:].W[c,:] + b[c]) (a D-long
 // dot product, block-reduced), then streams its slice of the plane.  Saves the separate gain launch + round trip.
@@ -332,25 +356,7 @@ __global__ __launch_bounds__(256) void film_scale_kernel(const float *__restrict
     __shared__ float wsum[4];
     const int64_t plane = blockIdx.y;
     const int o = (int)(plane / channels), c = (int)(plane - (int64_t)o * channels);
-    const float *h = head + (size_t)o * D, *w = weight + (size_t)c * D;
-    float acc = 0.0f;
-    // four strides of the dot product at a time, branch-free (clamped index, select afterwards): the eight loads are in flight together
-    // instead of one dependent round trip per stride, which is most of a workgroup's life when its slice of the plane is small
-    for (int d0 = threadIdx.x; d0 < D; d0 += 4 * blockDim.x) {
-        float wv[4], hv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int d = min(d0 + u * (int)blockDim.x, D - 1);
-            wv[u] = w[d];
-            hv[u] = h[d];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc += (d0 + u * (int)blockDim.x < D) ? wv[u] * hv[u] : 0.0f;
-    }
-    acc = aoc_wave_sum(acc);
-    if (aoc_lane() == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    const float g = 1.0f + tanhf((wsum[0] + wsum[1] + wsum[2] + wsum[3]) + (bias ? bias[c] : 0.0f));
+    const float g = film_gain_wg256(head + (size_t)o * D, weight + (size_t)c * D, bias, c, D, wsum);
     const float *xp = x + plane * hw;
     float *yp = y + plane * hw;
     const uintptr_t addr = reinterpret_cast<uintptr_t>(xp);
@@ -424,23 +430,7 @@ __global__ __launch_bounds__(256) void film_scale_ahead_kernel(const float *__re
             if (i < i1) v[u] = __builtin_nontemporal_load(x4 + i);
         }
     }
-    const float *h = head + (size_t)o * D, *w = weight + (size_t)c * D;
-    float acc = 0.0f;
-    for (int d0 = threadIdx.x; d0 < D; d0 += 4 * 256) {
-        float wv[4], hv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int d = min(d0 + u * 256, D - 1);
-            wv[u] = w[d];
-            hv[u] = h[d];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc += (d0 + u * 256 < D) ? wv[u] * hv[u] : 0.0f;
-    }
-    acc = aoc_wave_sum(acc);
-    if (aoc_lane() == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    const float g = 1.0f + tanhf((wsum[0] + wsum[1] + wsum[2] + wsum[3]) + (bias ? bias[c] : 0.0f));
+    const float g = film_gain_wg256(head + (size_t)o * D, weight + (size_t)c * D, bias, c, D, wsum);
     if (vec) {
         f32x4_t *y4 = reinterpret_cast<f32x4_t *>(yp + headn);
 #pragma unroll
@@ -456,6 +446,61 @@ __global__ __launch_bounds__(256) void film_scale_ahead_kernel(const float *__re
     } else {
         for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < hw; i += (int64_t)gridDim.x * 256) yp[i] = g * xp[i];
     }
+}
+
+// ---- streams whose source and destination planes may sit at different 16-byte misalignments ------------------------------------------
+// The plane is cut by the DESTINATION's alignment: up to three scalar floats in front, 16-byte non-temporal stores for the body, up to three
+// scalars behind.  Every source is loaded 16 bytes per lane through a vector type that promises the compiler 4-byte alignment only: one
+// global_load_dwordx4 whether the source plane sits at the destination's misalignment or at another one (with odd hw consecutive planes
+// alternate their misalignment, and three base pointers need not agree).  Nothing falls back to a scalar plane.
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+typedef f32x4_t f32x4_a4_t __attribute__((aligned(4)));
+__device__ __forceinline__ f32x4_t stream_load4(const float *p) { return __builtin_nontemporal_load(reinterpret_cast<const f32x4_a4_t *>(p)); }
+__device__ __forceinline__ int64_t floats_to_alignment(const void *p, int64_t hw) {
+    const int64_t n = ((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) / 4;
+    return n < hw ? n : hw;
+}
+
+// torch.cat([x, mem], 1) + IA_gate (decoding_module.py:193-194, :203-204) in one launch, modelled on film_scale_ahead_kernel: grid.y = plane
+// of y; the plane's source is a plane of x (c < Cx) or of mem; the workgroup's slice is requested before the dot product.  x and mem may be
+// the same tensor (both are only read).
+template <int U>
+__global__ __launch_bounds__(256) void cat_film_scale_kernel(const float *x, const float *mem, const float *__restrict__ head,
+                                                              const float *__restrict__ weight, const float *__restrict__ bias, int D, int Cx, int Cm,
+                                                              int64_t hw, int chunk, float *__restrict__ y) {
+    __shared__ float wsum[4];
+    const int C = Cx + Cm;
+    const int64_t plane = blockIdx.y;
+    const int o = (int)(plane / C), c = (int)(plane - (int64_t)o * C);
+    const float *sp = c < Cx ? x + ((int64_t)o * Cx + c) * hw : mem + ((int64_t)o * Cm + (c - Cx)) * hw;
+    float *yp = y + plane * hw;
+    const int64_t headn = floats_to_alignment(yp, hw);
+    const int64_t body4 = (hw - headn) / 4;
+    const int64_t i0 = (int64_t)blockIdx.x * chunk, i1 = min(body4, i0 + chunk);          // chunk = ceil((hw / 4) / gridDim.x) <= 256 U
+    const bool vec = i0 < i1;
+    f32x4_t v[U];
+    if (vec) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t i = i0 + threadIdx.x + u * 256;
+            if (i < i1) v[u] = stream_load4(sp + headn + 4 * i);
+        }
+    }
+    const int64_t tail0 = headn + body4 * 4;
+    float edge = 0.0f;                                                                    // the scalar in front or behind that this thread carries
+    const bool first = blockIdx.x == 0;
+    const int64_t e = threadIdx.x < headn ? threadIdx.x : tail0 + (threadIdx.x - headn);
+    const bool has_edge = first && e < hw && (threadIdx.x < headn || e >= tail0);
+    if (has_edge) edge = sp[e];
+    const float g = film_gain_wg256(head + (size_t)o * D, weight + (size_t)c * D, bias, c, D, wsum);
+    if (vec) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t i = i0 + threadIdx.x + u * 256;
+            if (i < i1) __builtin_nontemporal_store(v[u] * g, reinterpret_cast<f32x4_t *>(yp + headn + 4 * i));
+        }
+    }
+    if (has_edge) yp[e] = g * edge;
 }
 
 // ------------------------------------------------------------------------------------------ conditioning layer
@@ -786,6 +831,63 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float *__restrict__
             if (rp) v += rp[p];
             yp[p] = relu ? fmaxf(v, 0.0f) : v;
         }
+    }
+}
+
+// gn_apply_kernel with the gate that follows the Bottleneck folded in (decoding_module.py:196,198 / :206,208): y = g [relu](x a + b [+ residual]),
+// g from film_gain_wg256.  Per element the operations and their order are those of gn_apply_kernel followed by film_scale_ahead_kernel, so the
+// bits are those of the two launches.  16 bytes per lane (the plane cut by y's alignment as above); x (and the residual) are requested before
+// the dot product.  y may be x: every thread stores exactly the elements it loaded.
+template <int U>
+__global__ __launch_bounds__(256) void gn_apply_scale_kernel(const float *x, int C, int group_channels, int64_t hw, const float *__restrict__ stats,
+                                                              const float *__restrict__ gamma, const float *__restrict__ beta, const float *residual, int relu,
+                                                              const float *__restrict__ head, const float *__restrict__ weight,
+                                                              const float *__restrict__ gate_bias, int D, int chunk, float *y) {
+    __shared__ float wsum[4];
+    const int plane = blockIdx.y, c = plane % C, n = plane / C;
+    const int gi = n * (C / group_channels) + c / group_channels;
+    const float *xp = x + (size_t)plane * hw;
+    const float *rp = residual ? residual + (size_t)plane * hw : nullptr;
+    float *yp = y + (size_t)plane * hw;
+    const int64_t headn = floats_to_alignment(yp, hw);
+    const int64_t body4 = (hw - headn) / 4;
+    const int64_t i0 = (int64_t)blockIdx.x * chunk, i1 = min(body4, i0 + chunk);
+    const bool vec = i0 < i1;
+    f32x4_t v[U], r[U];
+    if (vec) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t i = i0 + threadIdx.x + u * 256;
+            if (i < i1) {
+                v[u] = stream_load4(xp + headn + 4 * i);
+                if (rp) r[u] = stream_load4(rp + headn + 4 * i);
+            }
+        }
+    }
+    const int64_t tail0 = headn + body4 * 4;
+    const int64_t e = threadIdx.x < headn ? threadIdx.x : tail0 + (threadIdx.x - headn);
+    const bool has_edge = blockIdx.x == 0 && e < hw && (threadIdx.x < headn || e >= tail0);
+    float ev = 0.0f, er = 0.0f;
+    if (has_edge) { ev = xp[e]; if (rp) er = rp[e]; }
+    const float mean = stats[2 * gi], rstd = stats[2 * gi + 1];
+    const float a = rstd * (gamma ? gamma[c] : 1.0f), b = (beta ? beta[c] : 0.0f) - mean * a;
+    const float g = film_gain_wg256(head + (size_t)n * D, weight + (size_t)c * D, gate_bias, c, D, wsum);
+    if (vec) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t i = i0 + threadIdx.x + u * 256;
+            if (i < i1) {
+                f32x4_t t = v[u] * a + b;
+                if (rp) t += r[u];
+                if (relu) { t.x = fmaxf(t.x, 0.0f); t.y = fmaxf(t.y, 0.0f); t.z = fmaxf(t.z, 0.0f); t.w = fmaxf(t.w, 0.0f); }
+                __builtin_nontemporal_store(t * g, reinterpret_cast<f32x4_t *>(yp + headn + 4 * i));
+            }
+        }
+    }
+    if (has_edge) {
+        float t = ev * a + b;
+        if (rp) t += er;
+        yp[e] = g * (relu ? fmaxf(t, 0.0f) : t);
     }
 }
 
@@ -1191,6 +1293,24 @@ int aoc_film_scale(const float *x, const float *head, const float *weight, const
     return AOC_OK;
 }
 
+int aoc_cat_film_scale(const float *x, const float *mem, const float *head, const float *weight, const float *bias, int n_obj, int head_dim, int Cx,
+                       int Cm, int64_t hw, float *y, aoc_stream_t stream) {
+    if (!x || !head || !weight || !y || n_obj < 1 || head_dim < 1 || Cx < 1 || Cm < 0 || hw < 1) return AOC_ERR_INVALID_ARG;
+    if (Cm > 0 && !mem) return AOC_ERR_INVALID_ARG;
+    const int64_t planes = (int64_t)n_obj * ((int64_t)Cx + Cm);
+    if (planes > 65535) return AOC_ERR_UNSUPPORTED;
+    const int U = hw / 4 <= 2048 ? 8 : 4;                      // as aoc_film_scale: one workgroup per half-resolution plane
+    const int64_t per_wg = 256 * (int64_t)U;
+    const unsigned gx = (unsigned)std::max<int64_t>(1, (hw / 4 + per_wg - 1) / per_wg);
+    const int chunk = (int)std::max<int64_t>(1, (hw / 4 + gx - 1) / gx);
+    if (U == 4)
+        hipLaunchKernelGGL(cat_film_scale_kernel<4>, dim3(gx, (unsigned)planes), dim3(256), 0, aoc_hip_stream(stream), x, mem, head, weight, bias, head_dim, Cx, Cm, hw, chunk, y);
+    else
+        hipLaunchKernelGGL(cat_film_scale_kernel<8>, dim3(gx, (unsigned)planes), dim3(256), 0, aoc_hip_stream(stream), x, mem, head, weight, bias, head_dim, Cx, Cm, hw, chunk, y);
+    AOC_RETURN_IF_LAUNCH_FAILED();
+    return AOC_OK;
+}
+
 struct CondWs {
     float *scores, *threshold, *partial, *part_scores;
     uint32_t *hist;
@@ -1268,6 +1388,31 @@ int aoc_groupnorm_relu(const float *x, int N, int C, int64_t hw, int groups, con
     hipLaunchKernelGGL(gn_stats_kernel, dim3((unsigned)(N * groups)), dim3(256), 0, st, x, C / groups, hw, eps, stats);
     hipLaunchKernelGGL(gn_apply_kernel, dim3((unsigned)((hw + 1023) / 1024), (unsigned)(N * C)), dim3(256), 0, st, x, C, C / groups, hw, stats, gamma, beta,
                        residual, relu, y);
+    AOC_RETURN_IF_LAUNCH_FAILED();
+    return AOC_OK;
+}
+
+int aoc_groupnorm_relu_scale(const float *x, int N, int C, int64_t hw, int groups, const float *gamma, const float *beta, float eps,
+                             const float *residual, int relu, const float *head, const float *weight, const float *gate_bias, int head_dim, float *y,
+                             void *workspace, size_t workspace_bytes, aoc_stream_t stream) {
+    if (!x || !y || !workspace || !head || !weight || N < 1 || C < 1 || hw < 1 || groups < 1 || head_dim < 1) return AOC_ERR_INVALID_ARG;
+    if (C % groups) return AOC_ERR_INVALID_ARG;
+    if ((int64_t)N * C > 65535ll) return AOC_ERR_UNSUPPORTED;                  // one grid row per plane (grid.y limit); nothing is enqueued
+    if (workspace_bytes < aoc_groupnorm_relu_workspace_bytes(N, groups)) return AOC_ERR_WORKSPACE;
+    hipStream_t st = aoc_hip_stream(stream);
+    float *stats = static_cast<float *>(workspace);
+    hipLaunchKernelGGL(gn_stats_kernel, dim3((unsigned)(N * groups)), dim3(256), 0, st, x, C / groups, hw, eps, stats);
+    const int U = hw / 4 <= 2048 ? 8 : 4;
+    const int64_t per_wg = 256 * (int64_t)U;
+    const unsigned gx = (unsigned)std::max<int64_t>(1, (hw / 4 + per_wg - 1) / per_wg);
+    const int chunk = (int)std::max<int64_t>(1, (hw / 4 + gx - 1) / gx);
+    const dim3 grid(gx, (unsigned)(N * C));
+    if (U == 4)
+        hipLaunchKernelGGL(gn_apply_scale_kernel<4>, grid, dim3(256), 0, st, x, C, C / groups, hw, stats, gamma, beta, residual, relu, head, weight, gate_bias,
+                           head_dim, chunk, y);
+    else
+        hipLaunchKernelGGL(gn_apply_scale_kernel<8>, grid, dim3(256), 0, st, x, C, C / groups, hw, stats, gamma, beta, residual, relu, head, weight, gate_bias,
+                           head_dim, chunk, y);
     AOC_RETURN_IF_LAUNCH_FAILED();
     return AOC_OK;
 }

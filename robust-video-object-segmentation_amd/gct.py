@@ -64,14 +64,22 @@ class Bottleneck(nn.Module):
     def _gn(bn, x, residual=None, relu=True):
         return ops.groupnorm_relu(x, bn.num_groups, bn.weight.detach(), bn.bias.detach(), bn.eps, residual, relu)
 
-    def forward(self, x):
+    def forward(self, x, gate=None):
+        """gate: None, or ``(IA_head, weight, bias)`` of the ``IA_gate`` that follows this block (decoding_module.py:196,198): the last
+        normalisation's apply pass then writes the gated tensor, bit-equal to calling the gate afterwards."""
         ops.inference_only("Bottleneck", x, *self.parameters())
         out = self._gn(self.bn1, self.conv1(self.GCT1(x)))                  # gct.py:69-72
         out = self._gn(self.bn2, self.conv2(out))                           # :74-76
         residual = x
         if self.downsample is not None:
             residual = self._gn(self.downsample[1], self.downsample[0](x), relu=False)     # :81-82
-        return self._gn(self.bn3, self.conv3(out), residual=residual)       # :78-79, 84-85
+        if gate is None:
+            return self._gn(self.bn3, self.conv3(out), residual=residual)   # :78-79, 84-85
+        head, weight, bias = gate
+        ops.inference_only("Bottleneck", head, weight, bias)
+        bn = self.bn3
+        return ops.groupnorm_relu_scale(self.conv3(out), bn.num_groups, bn.weight.detach(), bn.bias.detach(), bn.eps, residual, True,
+                                        head, weight.detach(), bias.detach() if bias is not None else None)
 
 
 def IA_logit(x, IA_head, IA_final):

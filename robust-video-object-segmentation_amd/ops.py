@@ -887,6 +887,35 @@ def film_scale(x, head, weight, bias, out=None):
     return y
 
 
+def _gate_shapes(what, n_obj, channels, head, weight, bias):
+    """A gate's head [n_obj, D], weight [channels, D] and bias [channels]: ValueError on a mismatch (no device is needed for it)."""
+    if head.dim() != 2 or weight.dim() != 2 or head.shape[0] != n_obj or weight.shape[1] != head.shape[1]:
+        raise ValueError(f"{what}: head {tuple(head.shape)} and weight {tuple(weight.shape)} do not fit {n_obj} objects")
+    if weight.shape[0] != channels or (bias is not None and bias.numel() != channels):
+        raise ValueError(f"{what}: the gate has {weight.shape[0]} rows, the tensor {channels} channels")
+
+
+def cat_film_scale(x, mem, head, weight, bias, out=None):
+    """torch.cat([x, mem], 1) gated by IA_gate in one launch (decoding_module.py:193-194, 203-204): bit-equal to
+    ``film_scale(torch.cat([x, mem], 1), head, weight, bias)``.  mem may be x itself (first frame) or None (plain film_scale)."""
+    x, head, weight = _f32c(x), _f32c(head), _f32c(weight)
+    mem = _f32c(mem) if mem is not None else None
+    bias = _f32c(bias) if bias is not None else None
+    n_obj, Cx = x.shape[0], x.shape[1]
+    Cm = mem.shape[1] if mem is not None else 0
+    if mem is not None and (mem.shape[0] != n_obj or mem.shape[2:] != x.shape[2:]):
+        raise ValueError(f"cat_film_scale: x {tuple(x.shape)} and the memory {tuple(mem.shape)} differ outside dim 1")
+    _gate_shapes("cat_film_scale", n_obj, Cx + Cm, head, weight, bias)
+    _need_gpu(x, mem, head, weight, bias)
+    hw = x.numel() // (n_obj * Cx)
+    shape = (n_obj, Cx + Cm) + tuple(x.shape[2:])
+    y = torch.empty(shape, dtype=torch.float32, device=x.device) if out is None else out
+    assert y.is_contiguous() and tuple(y.shape) == shape and y.dtype == torch.float32
+    _lib.check(_lib.lib().aoc_cat_film_scale(_p(x), _p(mem), _p(head), _p(weight), _p(bias), n_obj, head.shape[1], Cx, Cm, hw, _p(y), _stream()),
+               "aoc_cat_film_scale")
+    return y
+
+
 def cond_gate_pool(z, phi_w, phi_b, k_rank, want_debug=False, want_plane_mean=False):
     """CL:23-43 -> gap [N, C] (optionally also scores [N,HW] and threshold [N]; with want_plane_mean also the plane means [N, C] of z,
     CLB:68, from the same pass that computes the scores)."""
@@ -1082,6 +1111,28 @@ def groupnorm_relu(x, groups, gamma, beta, eps=1e-5, residual=None, relu=True, o
     b = _f32c(beta) if beta is not None else None
     _lib.check(L.aoc_groupnorm_relu(_p(x), N, C, hw, int(groups), _p(g), _p(b),
                                     float(eps), _p(residual), int(bool(relu)), _p(y), _p(ws), ws.numel(), _stream()), "aoc_groupnorm_relu")
+    return y
+
+
+def groupnorm_relu_scale(x, groups, gamma, beta, eps, residual, relu, head, weight, gate_bias, out=None):
+    """aoc_groupnorm_relu_scale: groupnorm_relu with the IA_gate that follows folded into its apply pass; bit-equal to
+    ``film_scale(groupnorm_relu(x, groups, gamma, beta, eps, residual, relu), head, weight, gate_bias)``."""
+    x, head, weight = _f32c(x), _f32c(head), _f32c(weight)
+    residual = _f32c(residual) if residual is not None else None
+    gate_bias = _f32c(gate_bias) if gate_bias is not None else None
+    N, C = x.shape[0], x.shape[1]
+    if int(groups) < 1 or C % int(groups):
+        raise ValueError(f"groupnorm_relu_scale: {C} channels do not divide into {groups} groups")
+    _gate_shapes("groupnorm_relu_scale", N, C, head, weight, gate_bias)
+    _need_gpu(x, gamma, beta, residual, head, weight, gate_bias)
+    hw = x.numel() // (N * C)
+    L = _lib.lib()
+    y = torch.empty_like(x) if out is None else out
+    ws = _ws(L.aoc_groupnorm_relu_workspace_bytes(N, int(groups)), x.device)
+    g = _f32c(gamma) if gamma is not None else None              # bound until the launch is enqueued (see groupnorm_relu)
+    b = _f32c(beta) if beta is not None else None
+    _lib.check(L.aoc_groupnorm_relu_scale(_p(x), N, C, hw, int(groups), _p(g), _p(b), float(eps), _p(residual), int(bool(relu)), _p(head), _p(weight),
+                                          _p(gate_bias), head.shape[1], _p(y), _p(ws), ws.numel(), _stream()), "aoc_groupnorm_relu_scale")
     return y
 
 
