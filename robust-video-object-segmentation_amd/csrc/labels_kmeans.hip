@@ -3,7 +3,6 @@
 #include "aoc_common.h"
 #include <stdlib.h>
 #include <algorithm>
-#include <string.h>
 
 namespace {
 
@@ -676,9 +675,7 @@ __global__ __launch_bounds__(256) void km_rownorm_kernel(const float *__restrict
 // tiles in a private, double-buffered, k-permuted LDS image (lane (j, kq) reads x[j][4t + kq] with ds_read_b128).
 // D: lane holds row j = lane & 15 and clusters (lane >> 4) * 4 + r: the argmin is 4 in-lane compares and two
 // cross-group exchanges, ties to the lowest index like scipy's strict <.
-#ifndef AOC_KA_TPF4
-#define AOC_KA_TPF4 1
-#endif
+constexpr int KA_TPF4 = 1;      // tiles in flight per wave at K > 48
 template <int TMAX, int KT>
 __global__ __launch_bounds__(256, KT == 1 ? 3 : 2) void km_assign_mfma_kernel(const float *__restrict__ pool, int C, const int32_t *__restrict__ rows,
                                                               const int32_t *__restrict__ seg_off, const int32_t *__restrict__ seg_k, int n_seg,
@@ -745,7 +742,7 @@ __global__ __launch_bounds__(256, KT == 1 ? 3 : 2) void km_assign_mfma_kernel(co
         }
         if (s >= n_seg) break;
         // ---- this item's rows: all loads of TPF tiles are issued before anything waits (ids -> pieces in registers)
-        constexpr int TPF = KT >= 4 ? AOC_KA_TPF4 : 2;       // tiles in flight per wave (K > 48: one -- the second set of staging registers spilled 36 VGPRs)
+        constexpr int TPF = KT >= 4 ? KA_TPF4 : 2;       // tiles in flight per wave (K > 48: one -- the second set of staging registers spilled 36 VGPRs)
         const int ibeg = seg_in_lds ? lseg_off[s] : seg_off[s], ilen = (seg_in_lds ? lseg_off[s + 1] : seg_off[s + 1]) - ibeg;
         const int wave_row0 = bx * 256 + wave * 64;
         float4 pv[TPF][PIECES];
@@ -1338,38 +1335,6 @@ __global__ __launch_bounds__(256) void km_scan_scatter_kernel(const int32_t *__r
 // from an any-order prefix of chunk sums; the serial stitch (km_sum_scan_kernel) verifies every prediction
 // against the exact running sum (same exponent, no overflow of n) and otherwise recomputes the chunk from the
 // rows, so a wrong prediction costs time, never exactness.
-constexpr int KC_TILE_LD = AOC_MAX_CHANNELS / 2 + 1;   // 129: row stride of the 64 x C LDS tile (C <= 128), conflict-free columns
-
-// Staging of 64-member blocks (full rows, coalesced 16-byte pieces) with memory-level parallelism: the chunk's
-// offsets sit in LDS, every thread issues all of its row loads for block b+1 before block b is consumed, and
-// writes them to the tile afterwards.  KC_STAGE_MAX float4 per thread cover 64 rows x C <= 128 floats.
-constexpr int KC_STAGE_MAX = (64 * (AOC_MAX_CHANNELS / 2 / 4) + 255) / 256;   // 8
-struct KcStage {
-    float4 v[KC_STAGE_MAX];
-};
-__device__ __forceinline__ void kc_issue_block(KcStage &st, const float *__restrict__ pool, const uint32_t *__restrict__ loffs, int blk,
-                                               int members_in_chunk, int c4) {
-#pragma unroll
-    for (int it = 0; it < KC_STAGE_MAX; ++it) {
-        const int idx = it * 256 + threadIdx.x;
-        const int mloc = idx / c4, piece = idx - mloc * c4;
-        const int m = blk * 64 + mloc;
-        st.v[it] = (idx < 64 * c4 && m < members_in_chunk)
-                       ? *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(pool) + loffs[m] + piece * 16)
-                       : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-}
-__device__ __forceinline__ void kc_write_block(const KcStage &st, float *__restrict__ tile, int c4) {
-#pragma unroll
-    for (int it = 0; it < KC_STAGE_MAX; ++it) {
-        const int idx = it * 256 + threadIdx.x;
-        if (idx < 64 * c4) {
-            const int mloc = idx / c4, piece = idx - mloc * c4;
-            float *d = tile + mloc * KC_TILE_LD + piece * 4;
-            d[0] = st.v[it].x; d[1] = st.v[it].y; d[2] = st.v[it].z; d[3] = st.v[it].w;
-        }
-    }
-}
 
 // P0: csum[chunk, f] = any-order float sum of the chunk's members (only used to predict binades).  Thread t owns the float4 piece
 // t % c4 of the rows t / c4, t / c4 + RPP, ... of the chunk (RPP = 256 / c4 rows per pass; consecutive threads read one row's consecutive
@@ -1418,15 +1383,6 @@ __device__ __forceinline__ void kc_chunk_sum_body(int chunk, uint32_t *__restric
         }
         *reinterpret_cast<float4 *>(csum + (size_t)chunk * C + 4 * threadIdx.x) = t;
     }
-}
-__global__ __launch_bounds__(256) void km_chunk_sum_kernel(const float *__restrict__ pool, int C, const int32_t *__restrict__ seg_off,
-                                                            const int32_t *__restrict__ counts, const int32_t *__restrict__ cbase,
-                                                            const uint32_t *__restrict__ moff, int kmax,
-                                                            const int32_t *__restrict__ owner_cluster, const int32_t *__restrict__ owner_local,
-                                                            float *__restrict__ csum, int start_chunk) {
-    __shared__ uint32_t loffs[KS_CHUNK];
-    __shared__ __attribute__((aligned(16))) float4 part[256];
-    kc_chunk_sum_body(blockIdx.x, loffs, part, pool, C, seg_off, counts, cbase, moff, kmax, owner_cluster, owner_local, csum, start_chunk);
 }
 
 // P1: per cluster, thread = feature: running any-order prefix over the chunks -> predicted binade of each chunk
@@ -2476,16 +2432,10 @@ __device__ __forceinline__ void os_ordered_sum_body(int j, int s, int grp, float
 // against 66 us).  Indices past the cluster's end are clamped to its last member (valid addresses, uniform operation counts); the last
 // batch adds +0.0f for them exactly as the zero rows of the version above did.  LDS rows are unpadded (112 B): transfer k of a producer
 // fills slots [64 k, 64 k + 64) of its half lane-linearly, slot j = piece j % 7 of member j / 7.
-#ifndef AOC_OD_NPROD
-#define AOC_OD_NPROD 3
-#endif
-#ifndef AOC_OD_DEPTH
-#define AOC_OD_DEPTH 1
-#endif
-constexpr int OD_NPROD = AOC_OD_NPROD;                         // producer waves
+constexpr int OD_NPROD = 3;                                    // producer waves
 constexpr int OD_HALF = 64;                                    // members per producer and step
 constexpr int OD_BATCH = OD_NPROD * OD_HALF;                   // members per step
-constexpr int OD_DEPTH = AOC_OD_DEPTH;                         // batches of row pieces in flight
+constexpr int OD_DEPTH = 1;                                    // batches of row pieces in flight
 constexpr int OD_NB = OD_DEPTH + 1;                            // ring slots (rows and offsets)
 constexpr int OD_LD = OS_FP * 4;                               // 28 floats per member
 constexpr int OD_BATCH_BYTES = OD_BATCH * OD_LD * 4;           // 14336
@@ -2656,8 +2606,8 @@ __global__ __launch_bounds__((OS_NPROD + 1) * 64) void km_ordered_sum_kernel(con
 // The literal heads and the any-order sums of the tail chunks only depend on the member lists, not on each other: ONE launch, the
 // first kmax * n_seg * groups workgroups take the heads (the long ones, dispatched first), the others one tail chunk each (on the
 // first four of their eight waves; the LDS allocation of the head role is reused).
-template <int MODE, bool DMA>
-__global__ __launch_bounds__(DMA ? 256 : (OS_NPROD + 1) * 64) void km_heads_chunk_sums_kernel(const float *__restrict__ pool, uint32_t pool_bytes, int C,
+template <int MODE>
+__global__ __launch_bounds__(256) void km_heads_chunk_sums_kernel(const float *__restrict__ pool, uint32_t pool_bytes, int C,
                                                                                    const int32_t *__restrict__ seg_off, const int32_t *__restrict__ seg_k,
                                                                                    const int32_t *__restrict__ counts, const int32_t *__restrict__ cbase,
                                                                                    const uint32_t *__restrict__ moff, int kmax, int n_seg, float *__restrict__ dst,
@@ -2667,7 +2617,7 @@ __global__ __launch_bounds__(DMA ? 256 : (OS_NPROD + 1) * 64) void km_heads_chun
                                                                                    KsPred pred, int spec_fold, int8_t *__restrict__ cexp,
                                                                                    int32_t *__restrict__ cinc0, int32_t *__restrict__ cinc1,
                                                                                    const int32_t *__restrict__ cchunk, int n_chunks_grid, int n_fold_groups) {
-    __shared__ __attribute__((aligned(16))) float os_lds[DMA ? (OD_LDS_FLOATS > 2 * OS_BATCH * OS_LD ? OD_LDS_FLOATS : 2 * OS_BATCH * OS_LD) : 2 * OS_BATCH * OS_LD];
+    __shared__ __attribute__((aligned(16))) float os_lds[OD_LDS_FLOATS > 2 * OS_BATCH * OS_LD ? OD_LDS_FLOATS : 2 * OS_BATCH * OS_LD];
     static_assert(sizeof(float) * 2 * OS_BATCH * OS_LD >= sizeof(uint32_t) * KS_CHUNK + sizeof(float4) * 256, "the chunk role's buffers fit the head role's");
     static_assert(2 * OS_BATCH * OS_LD >= KC_FOLD_LDS_FLOATS, "the fold role's buffers fit the head role's");
     const int n_head = kmax * n_seg * os_groups_dev(C);
@@ -2682,17 +2632,16 @@ __global__ __launch_bounds__(DMA ? 256 : (OS_NPROD + 1) * 64) void km_heads_chun
         const int blk = b / (8 * groups), rem = b - blk * (8 * groups);
         const int pc = min(8, n_cl - blk * 8);
         int grp = rem / pc, c = blk * 8 + rem - grp * pc;
-        if (!xcd_aware) { c = b % n_cl; grp = b / n_cl; }       // developer switch AOC_KM_XCD=0: the group-major order of before
+        if (!xcd_aware) { c = b % n_cl; grp = b / n_cl; }       // the group-major order of before (the host always passes 1)
         const int j = c % kmax, s = c / kmax;
-        if (DMA) os_head_dma_body<MODE>(j, s, grp, os_lds, pool, C, seg_off, seg_k, counts, cbase, moff, kmax, dst, member_cap, head_state, pred);
-        else os_ordered_sum_body<MODE>(j, s, grp, os_lds, pool, pool_bytes, C, seg_off, seg_k, counts, cbase, moff, kmax, dst, member_cap, head_state);
+        os_head_dma_body<MODE>(j, s, grp, os_lds, pool, C, seg_off, seg_k, counts, cbase, moff, kmax, dst, member_cap, head_state, pred);
         return;
     }
     if (threadIdx.x >= 256) return;
-    if (DMA && spec_fold) {
+    if (spec_fold) {
         // round 5: the tail chunks' integer folds in their PREDICTED binades (KsPred: the previous Lloyd iteration's) ride in this launch --
         // no any-order chunk sums, no separate fold launch; the stitch verifies every summary as before
-        static_assert(!DMA || OD_LDS_FLOATS >= KC_WIDE_LDS_FLOATS, "the wide fold's tile fits the heads' ring");
+        static_assert(OD_LDS_FLOATS >= KC_WIDE_LDS_FLOATS, "the wide fold's tile fits the heads' ring");
         kc_chunk_fold_wide_body(b - n_head, os_lds, pool, C, seg_off, counts, cbase, moff, kmax, owner_cluster, owner_local, cexp, cinc0, cinc1, start_chunk,
                                 n_chunks_grid, n_fold_groups, xcd_aware, pred);
         return;
@@ -2796,34 +2745,22 @@ inline KsWorkspace ks_carve(void *workspace, int64_t cap, int n_seg, int kmax, i
 }
 
 // Ordered per-cluster sums of the member lists in ws.moff -> dst (MODE 0 centroids / MODE 1 proxy set 1).
-//   "hybrid" (default): the first KS_HEAD_CHUNKS chunks of every cluster -- where the running sum crosses a binade at
-//             every doubling -- are summed literally, lanes = features (km_ordered_sum_kernel); larger clusters continue
-//             with the chunk-parallel integer folds and the serial stitch (their crossings are rare from there on);
-//   "ordered": literal sums only;   "scan": chunk-parallel pipeline only.   (AOC_KM_SUM, developer switch.)
+// The first KS_HEAD_CHUNKS chunks of every cluster -- where the running sum crosses a binade at every doubling -- are summed literally,
+// lanes = features (os_head_dma_body); larger clusters continue with the chunk-parallel integer folds and the serial stitch (their
+// crossings are rare from there on).  The variants this replaced -- literal sums only, the chunk-parallel pipeline only, heads and chunk
+// sums as two launches, the eight-wave heads without LDS-DMA, folds as a launch of their own, two or four features per stitch wave, the
+// group-major workgroup ids -- were measured and rejected (STATUS.md); commit dee710a is the last one that has them.
 // 20 chunks = 10240 members (12 until the sum kernels' XCD-aware ids; after them, three runs each at 12 / 20 / 28 chunks: cfg2 360.3 / 359.7 / 356.0,
 // cfg3 208.5 / 212.6 / 211.1, closed evaluation loop 246 / 251 / 239).  Alone, a chain is fastest at 5-6 chunks (sweep 1 .. 8 at R = 6: 3.13, 3.03, 2.90, 2.89, 2.76, 2.78, 2.81,
 // 2.84 ms per chain; 3.12 at 16): the heads share a launch with the tail's chunk sums and are off the critical path up to about
 // there.  In the bench, where the chains share the GPU with the other streams, what counts is the work a chain puts on the CUs, and the
 // literal heads (one adding wave per workgroup, a few cycles per member) are the cheapest way to sum a member: frames/s at
 // 2 / 3 / 4 / 6 / 8 / 10 / 12 / 16 / 24 / 32 / 64 chunks: cfg2 287 / 305 / 310 / 326 / 327 / 337 / 334 / 329 / 323 / 304 / 271, cfg3
-// 142 / 165 / 170 / 182 / 185 / 191 / 192 / 191 / 192 / 190 / 184.  AOC_KM_HEAD_CHUNKS: developer switch.  (A [4 members][feature] LDS layout
+// 142 / 165 / 170 / 182 / 185 / 191 / 192 / 191 / 192 / 190 / 184.  (A [4 members][feature] LDS layout
 // with one ds_read_b128 per four members shortens the adding wave's chain -- 3.0 -> 2.9 ms alone at 12 chunks -- but costs the seven
 // producer waves four ds_write_b32 per piece instead of one ds_write_b128: 1 % SLOWER in the bench, three runs each; not kept.)
-inline int km_xcd_aware() {
-    static const int on = AOC_DEV_ENV_INT("AOC_KM_XCD", 1) != 0;       // developer switch (counter comparisons)
-    return on;
-}
-static const int KS_HEAD_CHUNKS = AOC_DEV_ENV_INT("AOC_KM_HEAD_CHUNKS", 20) > 0 ? AOC_DEV_ENV_INT("AOC_KM_HEAD_CHUNKS", 20) : 20;
+constexpr int KS_HEAD_CHUNKS = 20;
 constexpr int KC_INLINE_PREDICT_CHUNKS = 800;   // 409 600 rows per segment
-inline int ks_sum_mode() {
-    static const int mode = [] {
-        const char *e = AOC_DEV_ENV("AOC_KM_SUM");
-        if (e && strcmp(e, "scan") == 0) return 0;
-        if (e && strcmp(e, "ordered") == 0) return 1;
-        return 2;
-    }();
-    return mode;
-}
 // spec: MODE 0, Lloyd iteration >= 1 -- the tail chunks are folded in the binades the previous iteration's stitch recorded (ws.pred), inside the
 // heads launch: FOUR launches per iteration (assignment, scan + scatter, heads + folds, stitch) and one pass over the tail rows instead of two.
 // Iteration 0 and the proxy sums (MODE 1: other rows, another workspace) have no previous stitch and take the any-order chunk sums + fold launch.
@@ -2833,122 +2770,58 @@ inline void ks_launch_sums(hipStream_t st, const float *pool, uint32_t pool_byte
     const KsPred no_pred = {nullptr, nullptr, nullptr};
     const KsPred pred = (MODE == 0) ? ws.pred : no_pred;             // MODE 0: every stitch (and every head without a tail) records for the next iteration
     const int n_fold_groups = (C + KC_FG - 1) / KC_FG;
-    // Where the folds run: INSIDE the heads launch (4 launches per iteration; smode 1).  A heads workgroup owns 43 KB of LDS, so three fit a CU, a
-    // cluster that fills its literal head keeps four of them for ~60 us, and the folds of the launch compete for the same slots; with the
-    // whole-chunk staging of kc_chunk_fold_wide_body that still beats heads + folds as two launches (smode 2, development switch) and the
-    // five-launch iteration of round 4 (smode 0) alone at every size measured (profiles/r05_kmeans_spec_fold_ab.txt: cfg2 R = 6, three frames per
-    // chain 3.7-3.8 -> 3.1 ms; cfg3 R = 2 4.9 -> 4.1; cfg4 R = 3 7.4 -> 6.7) except cfg3 at R = 6 on one of two boxes (10.7 -> 11.1 ms there, 12.3 -> 11.2
-    // on the other: the K = 8 level has ~200 clusters that fill their head, more head workgroups than slots).
-    int smode = spec ? 1 : 0;
+    const int start = KS_HEAD_CHUNKS, head_cap = KS_HEAD_CHUNKS * KS_CHUNK;
+    const unsigned n_head_wg = (unsigned)(kmax * n_seg * os_groups(C));
+    auto stitch = [&] {
+        hipLaunchKernelGGL((km_sum_scan_kernel<MODE, 1>), dim3((unsigned)((C + KS_SCAN_WAVES - 1) / KS_SCAN_WAVES) * kmax * n_seg), dim3(KS_SCAN_WAVES * 64), 0, st, pool,
+                           pool_bytes, C, seg_offsets, seg_k, counts, ws.cbase, ws.moff, kmax, dst, ws.cchunk, ws.cexp, ws.cinc0, ws.cinc1, start, ws.head, n_seg, 1, pred);
+    };
 #ifdef AOC_DEV
-    static const int spec_env = AOC_DEV_ENV_INT("AOC_KM_SPEC", -1);      // developer switch: 0 = the five-launch iteration of round 4, 1 = folds in the heads launch, 2 = folds apart
-    if (spec && spec_env >= 0) smode = spec_env;
-    if (!(ks_sum_mode() == 2 && AOC_DEV_ENV_INT("AOC_KM_FUSED", 0) != 1 && AOC_DEV_ENV_INT("AOC_KM_HEADS_DMA", 1) != 0 &&
-          !(AOC_DEV_ENV("AOC_KM_HEADS") && strcmp(AOC_DEV_ENV("AOC_KM_HEADS"), "kernel") == 0)))
-        smode = 0;
-#endif
-    if (!(MODE == 0 && C <= KC_FG * 8)) smode = 0;
-    if (smode != 0) {
-        const int start = KS_HEAD_CHUNKS;
-        const unsigned n_head_wg = (unsigned)(kmax * n_seg * os_groups(C));
-        hipLaunchKernelGGL((km_heads_chunk_sums_kernel<MODE, true>), dim3(n_head_wg + (smode == 1 ? (unsigned)ws.nch_cap * n_fold_groups : 0u)), dim3(256), 0, st, pool,
-                           pool_bytes, C, seg_offsets, seg_k, counts, ws.cbase, ws.moff, kmax, n_seg, dst, KS_HEAD_CHUNKS * KS_CHUNK, ws.head, ws.owner_cluster,
-                           ws.owner_local, ws.csum, start, km_xcd_aware(), pred, 1, ws.cexp, ws.cinc0, ws.cinc1, ws.cchunk, ws.nch_cap, n_fold_groups);
-        if (smode == 2)
-            hipLaunchKernelGGL(km_chunk_fold_kernel, dim3((unsigned)ws.nch_cap * n_fold_groups), dim3(256), 0, st, pool, C, seg_offsets, counts, ws.cbase, ws.moff,
-                               kmax, ws.owner_cluster, ws.owner_local, ws.cexp, ws.cinc0, ws.cinc1, start, (const float *)nullptr, ws.cchunk, ws.head, ws.nch_cap,
-                               n_fold_groups, km_xcd_aware(), pred);
-        hipLaunchKernelGGL((km_sum_scan_kernel<MODE, 1>), dim3((unsigned)((C + KS_SCAN_WAVES - 1) / KS_SCAN_WAVES) * kmax * n_seg), dim3(KS_SCAN_WAVES * 64), 0, st, pool, pool_bytes, C, seg_offsets, seg_k, counts, ws.cbase,
-                           ws.moff, kmax, dst, ws.cchunk, ws.cexp, ws.cinc0, ws.cinc1, start, ws.head, n_seg, km_xcd_aware(), pred);
+    // developer switch AOC_KM_FUSED=1: capped literal heads by the eight-wave km_ordered_sum_kernel, then km_chunk_scanfold_kernel instead of
+    // chunk sum -> predict -> fold, and no speculative folds.  Bit-identical (all k-means tests pass in both modes); measured 3.5 vs 3.9 ms
+    // per 20-iteration chain at R = 6 with one frame per chain, but 6.6 vs 6.4 ms with three frames per chain and 5.7 vs 5.6 at R = 12:
+    // workgroups that wait for their predecessors' sums hold CU slots, so the product stays the three-kernel tail.
+    static const bool fused = AOC_DEV_ENV_INT("AOC_KM_FUSED", 0) == 1;
+    if (fused && C <= KC_FG * 8) {
+        hipLaunchKernelGGL(km_ordered_sum_kernel<MODE>, dim3(kmax, n_seg, os_groups(C)), dim3((OS_NPROD + 1) * 64), 0, st, pool, pool_bytes, C, seg_offsets,
+                           seg_k, counts, ws.cbase, ws.moff, kmax, dst, head_cap, ws.head);
+        hipLaunchKernelGGL(km_chunk_scanfold_kernel, dim3(ws.nch_cap, n_fold_groups), dim3(256), 0, st, pool, C, seg_offsets, counts, ws.cbase,
+                           ws.moff, kmax, ws.owner_cluster, ws.owner_local, ws.cchunk, ws.head, ws.csum, ws.cflag, ws.cexp, ws.cinc0, ws.cinc1, start);
+        stitch();
         return;
     }
-#ifndef AOC_DEV
-    // release build: literal heads by LDS-DMA + any-order chunk sums in one launch, then the fold (binade prediction inside it while no cluster
-    // can have more than KC_INLINE_PREDICT_CHUNKS chunks) -- the alternatives below only exist in the development build
-    const int start = KS_HEAD_CHUNKS;
-    hipLaunchKernelGGL((km_heads_chunk_sums_kernel<MODE, true>), dim3(kmax * n_seg * os_groups(C) + ws.nch_cap), dim3(256), 0, st, pool, pool_bytes, C,
-                       seg_offsets, seg_k, counts, ws.cbase, ws.moff, kmax, n_seg, dst, KS_HEAD_CHUNKS * KS_CHUNK, ws.head, ws.owner_cluster, ws.owner_local,
-                       ws.csum, start, 1, pred, 0, ws.cexp, ws.cinc0, ws.cinc1, ws.cchunk, ws.nch_cap, n_fold_groups);
-    {
+#endif
+    if (spec && MODE == 0 && C <= KC_FG * 8) {
+        // Where the folds run: INSIDE the heads launch (4 launches per iteration).  A heads workgroup owns 43 KB of LDS, so three fit a CU, a
+        // cluster that fills its literal head keeps four of them for ~60 us, and the folds of the launch compete for the same slots; with the
+        // whole-chunk staging of kc_chunk_fold_wide_body that still beats heads + folds as two launches and the five-launch iteration of
+        // round 4 alone at every size measured (profiles/r05_kmeans_spec_fold_ab.txt: cfg2 R = 6, three frames per
+        // chain 3.7-3.8 -> 3.1 ms; cfg3 R = 2 4.9 -> 4.1; cfg4 R = 3 7.4 -> 6.7) except cfg3 at R = 6 on one of two boxes (10.7 -> 11.1 ms there, 12.3 -> 11.2
+        // on the other: the K = 8 level has ~200 clusters that fill their head, more head workgroups than slots).
+        hipLaunchKernelGGL(km_heads_chunk_sums_kernel<MODE>, dim3(n_head_wg + (unsigned)ws.nch_cap * n_fold_groups), dim3(256), 0, st, pool, pool_bytes, C,
+                           seg_offsets, seg_k, counts, ws.cbase, ws.moff, kmax, n_seg, dst, head_cap, ws.head, ws.owner_cluster, ws.owner_local,
+                           ws.csum, start, 1, pred, 1, ws.cexp, ws.cinc0, ws.cinc1, ws.cchunk, ws.nch_cap, n_fold_groups);
+    } else {
+        // literal heads by LDS-DMA + any-order chunk sums in one launch, then the fold.  The binade prediction runs inside the fold kernel
+        // (every workgroup re-adds its cluster's earlier chunk sums: quadratic in the chunks of a cluster, so only while a cluster cannot
+        // have more than KC_INLINE_PREDICT_CHUNKS), beyond that as a launch of its own
+        hipLaunchKernelGGL(km_heads_chunk_sums_kernel<MODE>, dim3(n_head_wg + ws.nch_cap), dim3(256), 0, st, pool, pool_bytes, C,
+                           seg_offsets, seg_k, counts, ws.cbase, ws.moff, kmax, n_seg, dst, head_cap, ws.head, ws.owner_cluster, ws.owner_local,
+                           ws.csum, start, 1, pred, 0, ws.cexp, ws.cinc0, ws.cinc1, ws.cchunk, ws.nch_cap, n_fold_groups);
         const bool inline_predict = ws.seg_chunks_max <= KC_INLINE_PREDICT_CHUNKS;
         if (!inline_predict)
             hipLaunchKernelGGL(km_chunk_predict_kernel, dim3(kmax, n_seg), dim3(128), 0, st, seg_k, counts, ws.cchunk, ws.csum, kmax, C, ws.cexp, start, ws.head);
-        hipLaunchKernelGGL(km_chunk_fold_kernel, dim3((unsigned)ws.nch_cap * ((C + KC_FG - 1) / KC_FG)), dim3(256), 0, st, pool, C, seg_offsets, counts, ws.cbase, ws.moff,
+        hipLaunchKernelGGL(km_chunk_fold_kernel, dim3((unsigned)ws.nch_cap * n_fold_groups), dim3(256), 0, st, pool, C, seg_offsets, counts, ws.cbase, ws.moff,
                            kmax, ws.owner_cluster, ws.owner_local, ws.cexp, ws.cinc0, ws.cinc1, start, inline_predict ? ws.csum : (const float *)nullptr,
-                           ws.cchunk, ws.head, ws.nch_cap, (C + KC_FG - 1) / KC_FG, 1, no_pred);
+                           ws.cchunk, ws.head, ws.nch_cap, n_fold_groups, 1, no_pred);
     }
-#else
-    const int mode = ks_sum_mode();
-    const int start = (mode == 2) ? KS_HEAD_CHUNKS : 0;
-    static const bool fused = AOC_DEV_ENV_INT("AOC_KM_FUSED", 0) == 1;
-    static const bool split_heads = AOC_DEV_ENV("AOC_KM_HEADS") && strcmp(AOC_DEV_ENV("AOC_KM_HEADS"), "kernel") == 0;   // developer switch: heads and chunk sums as two launches
-    const bool merged = (mode == 2) && !(fused && C <= KC_FG * 8) && !split_heads;
-    if (merged) {
-        // literal heads on one wave per (cluster, feature group) with LDS-DMA row transfers (os_head_dma_body); developer switch
-        // AOC_KM_HEADS_DMA=0: the eight-wave producer / consumer version of rounds 2-3
-        static const bool dma = AOC_DEV_ENV_INT("AOC_KM_HEADS_DMA", 1) != 0;
-        if (dma)
-            hipLaunchKernelGGL((km_heads_chunk_sums_kernel<MODE, true>), dim3(kmax * n_seg * os_groups(C) + ws.nch_cap), dim3(256), 0, st, pool, pool_bytes, C,
-                               seg_offsets, seg_k, counts, ws.cbase, ws.moff, kmax, n_seg, dst, KS_HEAD_CHUNKS * KS_CHUNK, ws.head, ws.owner_cluster, ws.owner_local,
-                               ws.csum, start, km_xcd_aware(), pred, 0, ws.cexp, ws.cinc0, ws.cinc1, ws.cchunk, ws.nch_cap, n_fold_groups);
-        else
-            hipLaunchKernelGGL((km_heads_chunk_sums_kernel<MODE, false>), dim3(kmax * n_seg * os_groups(C) + ws.nch_cap), dim3((OS_NPROD + 1) * 64), 0, st, pool, pool_bytes, C,
-                               seg_offsets, seg_k, counts, ws.cbase, ws.moff, kmax, n_seg, dst, KS_HEAD_CHUNKS * KS_CHUNK, ws.head, ws.owner_cluster, ws.owner_local,
-                               ws.csum, start, km_xcd_aware(), pred, 0, ws.cexp, ws.cinc0, ws.cinc1, ws.cchunk, ws.nch_cap, n_fold_groups);
-    } else if (mode != 0) {
-        const int cap = (mode == 2) ? KS_HEAD_CHUNKS * KS_CHUNK : 0;
-        hipLaunchKernelGGL(km_ordered_sum_kernel<MODE>, dim3(kmax, n_seg, os_groups(C)), dim3((OS_NPROD + 1) * 64), 0, st, pool, pool_bytes, C, seg_offsets,
-                           seg_k, counts, ws.cbase, ws.moff, kmax, dst, cap, ws.head);
-        if (mode == 1) return;
-    }
-    // developer switch AOC_KM_FUSED=1: km_chunk_scanfold_kernel instead of chunk sum -> predict -> fold.  Bit-identical (all k-means tests
-    // pass in both modes); measured 3.5 vs 3.9 ms per 20-iteration chain at R = 6 with one frame per chain, but 6.6 vs 6.4 ms with three
-    // frames per chain and 5.7 vs 5.6 at R = 12: workgroups that wait for their predecessors' sums hold CU slots, so the default stays
-    // the three-kernel tail.
-    if (fused && C <= KC_FG * 8) {
-        hipLaunchKernelGGL(km_chunk_scanfold_kernel, dim3(ws.nch_cap, (C + KC_FG - 1) / KC_FG), dim3(256), 0, st, pool, C, seg_offsets, counts, ws.cbase,
-                           ws.moff, kmax, ws.owner_cluster, ws.owner_local, ws.cchunk, ws.head, ws.csum, ws.cflag, ws.cexp, ws.cinc0, ws.cinc1, start);
-    } else {
-        if (!merged)
-            hipLaunchKernelGGL(km_chunk_sum_kernel, dim3(ws.nch_cap), dim3(256), 0, st, pool, C, seg_offsets, counts, ws.cbase, ws.moff, kmax, ws.owner_cluster,
-                               ws.owner_local, ws.csum, start);
-        // the binade prediction runs inside the fold kernel (every workgroup re-adds its cluster's earlier chunk sums: quadratic in the
-        // chunks of a cluster, so only while a cluster cannot have more than KC_INLINE_PREDICT_CHUNKS); AOC_KM_PREDICT=kernel: separate launch
-        static const bool sep_predict = AOC_DEV_ENV("AOC_KM_PREDICT") && strcmp(AOC_DEV_ENV("AOC_KM_PREDICT"), "kernel") == 0;
-        const bool inline_predict = !sep_predict && ws.seg_chunks_max <= KC_INLINE_PREDICT_CHUNKS;
-        if (!inline_predict)
-            hipLaunchKernelGGL(km_chunk_predict_kernel, dim3(kmax, n_seg), dim3(128), 0, st, seg_k, counts, ws.cchunk, ws.csum, kmax, C, ws.cexp, start, ws.head);
-        hipLaunchKernelGGL(km_chunk_fold_kernel, dim3((unsigned)ws.nch_cap * ((C + KC_FG - 1) / KC_FG)), dim3(256), 0, st, pool, C, seg_offsets, counts, ws.cbase, ws.moff,
-                           kmax, ws.owner_cluster, ws.owner_local, ws.cexp, ws.cinc0, ws.cinc1, start, inline_predict ? ws.csum : (const float *)nullptr,
-                           ws.cchunk, ws.head, ws.nch_cap, (C + KC_FG - 1) / KC_FG, km_xcd_aware(), no_pred);
-    }
-#endif
-    static const int nf = AOC_DEV_ENV_INT("AOC_KS_NF", 1);       // features per stitch wave (developer switch)
-#define AOC_KSS(NF) hipLaunchKernelGGL((km_sum_scan_kernel<MODE, NF>), dim3((unsigned)((C / NF + KS_SCAN_WAVES - 1) / KS_SCAN_WAVES) * kmax * n_seg), dim3(KS_SCAN_WAVES * 64), 0, st, pool, pool_bytes, C, seg_offsets, seg_k, \
-                                       counts, ws.cbase, ws.moff, kmax, dst, ws.cchunk, ws.cexp, ws.cinc0, ws.cinc1, start, ws.head, n_seg, km_xcd_aware(), pred)
-#ifdef AOC_DEV
-    if (nf == 4) AOC_KSS(4); else if (nf == 2) AOC_KSS(2); else AOC_KSS(1);
-#else
-    (void)nf;
-    AOC_KSS(1);
-#endif
-#undef AOC_KSS
+    stitch();
 }
 
-#ifndef AOC_KM_REP64
-#define AOC_KM_REP64 0
-#endif
-// LDS a workgroup of the replica-fused assignment may use: half a CU's (two workgroups per CU; three at K <= 16) -- or, for K = 64 (four cluster tiles: two
-// 30 KB code books do not fit half a CU), a whole CU's with AOC_KM_REP64 (one workgroup of four waves per CU then stages the rows once for up to four code books)
-inline size_t km_rep_lds_budget(int kt) {
-    static const bool rep64 = AOC_DEV_ENV_INT("AOC_KM_REP64", AOC_KM_REP64) != 0;
-    return (kt == 4 && rep64) ? (size_t)150 * 1024 : (size_t)78 * 1024;
-}
-
-inline int km_assign_grid_cap() {
-    static const int cap = AOC_DEV_ENV_INT("AOC_KM_ASSIGN_GRID", 512);      // developer switch (measured: 128 .. 512 within 3 %)
-    return cap > 0 ? cap : 512;
-}
+// LDS a workgroup of the replica-fused assignment may use: half a CU's (two workgroups per CU; three at K <= 16).  (K = 64 with a whole CU's: measured slower,
+// removed with the variants above.)
+constexpr size_t KM_REP_LDS_BUDGET = (size_t)78 * 1024;
+constexpr int KM_ASSIGN_GRID_CAP = 512;      // measured: 128 .. 512 within 3 %
 
 inline int label_blocks(int64_t n) { return (int)((n + LP_BLOCK - 1) / LP_BLOCK); }
 
@@ -3039,7 +2912,6 @@ int aoc_kmeans_segmented_rep(const float *pool, int64_t pool_rows, int C, const 
     // scan-sum pipeline: rows addressed by 32-bit byte offsets through a bounds-checked buffer descriptor
     const bool fast = (C % 4) == 0 && C <= 128 && pool_rows > 0 && (uint64_t)pool_rows * C * 4 < 0xFFFFFF00ull;
     const uint32_t pool_bytes = fast ? (uint32_t)((uint64_t)pool_rows * C * 4) : 0u;
-    static const bool mfma_assign = !(AOC_DEV_ENV("AOC_KM_ASSIGN") && strcmp(AOC_DEV_ENV("AOC_KM_ASSIGN"), "valu") == 0);   // developer switch
 
     hipLaunchKernelGGL(km_init_kernel, dim3(kmax, n_seg), dim3(64), 0, st, pool, C, rows, seg_offsets, seg_k, init_rows, kmax,
                        centroids, cnorm, cluster_counts);
@@ -3048,13 +2920,13 @@ int aoc_kmeans_segmented_rep(const float *pool, int64_t pool_rows, int C, const 
     const size_t lds = ((size_t)kmax * C + kmax) * sizeof(float);
     const size_t lds_fast = lds + (size_t)4 * kmax * sizeof(int32_t);
     const int nf = (C + 63) / 64;
-    const bool use_mfma = fast && mfma_assign && C == 100 && kmax <= 64;
+    const bool use_mfma = fast && C == 100 && kmax <= 64;
     if (use_mfma) {
         // row norms up front (replicated lists whose assignment is fused: replica 0's entries are the ones read), so that the first iteration
         // takes the matrix-pipe kernel as well
         const size_t per_r = ((size_t)((kmax + 15) / 16) * 16 * 116 + ((kmax + 15) / 16) * 16) * sizeof(float) + 256;
         const size_t fixed_r = (size_t)4 * 16 * 116 * sizeof(float) + (size_t)4 * kmax * sizeof(int32_t);
-        const bool rep_path = n_rep > 1 && (km_rep_lds_budget((kmax + 15) / 16) - fixed_r) / per_r >= 2 && AOC_DEV_ENV_INT("AOC_KM_ASSIGN_REP", 1) != 0;
+        const bool rep_path = n_rep > 1 && (KM_REP_LDS_BUDGET - fixed_r) / per_r >= 2;
         const int lim = rep_path ? n_seg / n_rep : n_seg;
         const int64_t bound = rep_path ? std::min<int64_t>(rows_capacity / n_rep + 1, rows_capacity) : rows_capacity;
         hipLaunchKernelGGL(km_rownorm_kernel, dim3((unsigned)((bound + 255) / 256)), dim3(256), 0, st, pool, C, rows, seg_offsets, lim, rownorm);
@@ -3064,16 +2936,15 @@ int aoc_kmeans_segmented_rep(const float *pool, int64_t pool_rows, int C, const 
         if (use_mfma) {
             const int kt = (kmax + 15) / 16;
             // K <= 16: the kernels are built for three workgroups per CU (168 registers, <= 53 KB of LDS): 768 resident workgroups instead of 512
-            const int64_t gcap = kt == 1 ? (int64_t)km_assign_grid_cap() * 3 / 2 : km_assign_grid_cap();
+            const int64_t gcap = kt == 1 ? (int64_t)KM_ASSIGN_GRID_CAP * 3 / 2 : KM_ASSIGN_GRID_CAP;
             bool rep_done = false;
             // replicated segment lists: the rows of a block are staged once for a group of replicas (km_assign_mfma_rep_kernel) as long as
             // at least two code books fit next to the row images in half a CU's LDS
             {
                 const size_t fixed = (size_t)4 * 16 * 116 * sizeof(float) + (size_t)4 * kmax * sizeof(int32_t);
                 const size_t per = ((size_t)kt * 16 * 116 + kt * 16) * sizeof(float) + 256;
-                const int fit = (int)std::min<size_t>(16, (km_rep_lds_budget(kt) - fixed) / per);
-                static const bool rep_off = AOC_DEV_ENV_INT("AOC_KM_ASSIGN_REP", 1) == 0;     // developer switch
-                if (n_rep > 1 && fit >= 2 && !rep_off) {
+                const int fit = (int)std::min<size_t>(16, (KM_REP_LDS_BUDGET - fixed) / per);
+                if (n_rep > 1 && fit >= 2) {
                     const int n_groups = (n_rep + fit - 1) / fit;
                     const int n_grp = (n_rep + n_groups - 1) / n_groups;
                     const int n_base = n_seg / n_rep;
@@ -3083,7 +2954,7 @@ int aoc_kmeans_segmented_rep(const float *pool, int64_t pool_rows, int C, const 
 #define AOC_KAR(KT)                                                                                                                                        \
     do {                                                                                                                                                   \
         static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(km_assign_mfma_rep_kernel<25, KT>),                                     \
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)km_rep_lds_budget(KT) + 2048) == hipSuccess;           \
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)KM_REP_LDS_BUDGET + 2048) == hipSuccess;              \
         if (!ok) return AOC_ERR_LAUNCH;                                                                                                                    \
         hipLaunchKernelGGL((km_assign_mfma_rep_kernel<25, KT>), dim3(rgrid), dim3(256), rlds, st, pool, C, rows, seg_offsets, seg_k, n_base, n_rep, n_grp, \
                            centroids, kmax, labels, ws.rank16, ws.hist, ws.nb_max, rownorm);                                                               \
