@@ -621,6 +621,40 @@ int aoc_groupnorm_relu_scale(const float *x, int N, int C, int64_t hw, int group
                              aoc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * ASPP, networks/layers/aspp.py:7-70 (the module CalibrationDecoding runs between IA9 and Modulator_1, decoding_module.py:53, :131): what is
+ * not a convolution.  fp32.  Every argument is validated before the first launch (no device needed for a rejection).  Pointer lists are HOST
+ * arrays of at most 8 device pointers; they are copied into the kernel's arguments, so the array may be freed when the call returns.
+ *
+ * One pass over x [planes, hw]: sum[p] = sum of x, sumsq[p] = sum of x^2, mean[p] = sum[p] / (float)hw.  Replaces the four
+ * x.pow(2).sum((2, 3)) of aspp.py:19 (via gct.py:19: aspp1..4.GCT read the same x) and the AdaptiveAvgPool2d of aspp.py:46.  Any of the three
+ * outputs may be NULL, not all of them.  Fixed summation order, no atomics: the same bits on every run (the order follows the 16-byte
+ * alignment of x's planes, so "the same" includes the base pointer modulo 16). */
+int aoc_plane_sum_sumsq(const float *x, int64_t planes, int64_t hw, float *sum, float *sumsq, float *mean, aoc_stream_t stream);
+/* aoc_gct_gate for n_sets parameter sets over one plane_sums [N, C] in one launch (the gates of aspp1..4.GCT, aspp.py:19 via gct.py:17-34):
+ * alpha, gamma, beta [n_sets, C]; gate [n_sets, N, C]; set k carries exactly the bits of aoc_gct_gate with row k of the parameters. */
+int aoc_gct_gate_multi(const float *plane_sums, const float *alpha, const float *gamma, const float *beta, int n_sets, int N, int C,
+                       float eps, int l1_mode, float *gate, aoc_stream_t stream);
+/* y_k[p, :] = gains[k, p] * x[p, :] for k < n_out <= 8 with x [planes, hw] read once (the x * gate of gct.py:36 for aspp1..4.GCT, aspp.py:19):
+ * gains [n_out, planes]; y_ptrs: n_out pointers to [planes, hw].  Each y_k carries the bits of aoc_channel_scale.  16 bytes per lane whatever
+ * the 16-byte misalignments of x and of the y_k are.  y_0 may be x itself when n_out == 1; every other overlap is rejected. */
+int aoc_channel_scale_multi(const float *x, const float *gains, int n_out, int64_t planes, int64_t hw, float *const *y_ptrs,
+                            aoc_stream_t stream);
+/* aspp.py:21-23 for the four branches and the concatenation of :62-63 as a statistics launch and an apply launch:
+ *   y[n, k C_src + c]     = [relu]( GroupNorm_groups(x_k)[n, c] * gamma[k, c] + beta[k, c] )     k < n_src <= 8
+ *   y[n, n_src C_src + c] = [relu]( tail[n, c] )  over the whole plane                            c < C_tail
+ * x_ptrs: n_src pointers to [N, C_src, hw]; gamma, beta [n_src, C_src] or NULL; tail [N, C_tail] (NULL with C_tail = 0) is the pooled branch of
+ * :61 -- F.interpolate(..., align_corners=True) from a 1 x 1 map (:62) is a broadcast, the expanded tensor is never materialised;
+ * y [N, n_src C_src + C_tail, hw] overlaps no input (x_k, tail, gamma, beta), nor plane_sumsq or the workspace, which overlap nothing either
+ * (all checked: AOC_ERR_INVALID_ARG).  The statistics are those of aoc_groupnorm_relu (same routine, every source in one
+ * launch), so y carries the bits of torch.cat([aoc_groupnorm_relu(x_k) ..., tail expanded], 1).  plane_sumsq [N, n_src C_src + C_tail] (may be
+ * NULL) = sum over each plane of y^2, accumulated from the values being stored in a fixed order: the plane sums GCT(640) needs (:65 via
+ * gct.py:19) without another read of y; deterministic (for one alignment of y modulo 16), not the bits of aoc_plane_reduce. */
+size_t aoc_groupnorm_cat_relu_workspace_bytes(int n_src, int N, int groups);
+int aoc_groupnorm_cat_relu(const float *const *x_ptrs, int n_src, int N, int C_src, int64_t hw, int groups, const float *gamma,
+                           const float *beta, float eps, const float *tail, int C_tail, int relu, float *y, float *plane_sumsq,
+                           void *workspace, size_t workspace_bytes, aoc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Eval-loop memory policy (the caller of the matching path).
  *
  * aoc_confident_labels: the per-pixel decision of one frame, eval_manager_mm.py:253-265,300-326,339-346,357-361 with

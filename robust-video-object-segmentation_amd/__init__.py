@@ -35,6 +35,7 @@ from . import gct  # noqa: F401,E402
 from . import eval_runner  # noqa: F401,E402
 from . import decoder_tail  # noqa: F401,E402
 from . import decoder_memory  # noqa: F401,E402
+from . import aspp  # noqa: F401,E402
 
 __all__ = ["synthetic", "ops", "matching", "attention", "conditioning_layer", "hotpath", "sharding", "eval_loop", "gct", "eval_runner", "decoder_tail",
-           "decoder_memory"]
+           "decoder_memory", "aspp"]

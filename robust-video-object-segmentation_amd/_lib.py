@@ -114,6 +114,11 @@ SIGNATURES = {
     "aoc_shortcut_stage_enqueue": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "aoc_logit_head": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i64, _vp, _vp]),
     "aoc_background_merge": (_i, [_vp, _vp, _i, _i64, _vp, _vp]),
+    "aoc_plane_sum_sumsq": (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "aoc_gct_gate_multi": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _vp]),
+    "aoc_channel_scale_multi": (_i, [_vp, _vp, _i, _i64, _i64, _vp, _vp]),
+    "aoc_groupnorm_cat_relu_workspace_bytes": (_sz, [_i, _i, _i]),
+    "aoc_groupnorm_cat_relu": (_i, [_vp, _i, _i, _i, _i64, _i, _vp, _vp, _f, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
 }
 
 STATUS = {0: "AOC_OK", -1: "AOC_ERR_INVALID_ARG", -2: "AOC_ERR_WORKSPACE", -3: "AOC_ERR_LAUNCH", -4: "AOC_ERR_UNSUPPORTED"}

@@ -1173,6 +1173,240 @@ __global__ __launch_bounds__(PH_PIX) void prehead_apply_kernel(const float *__re
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// ASPP (networks/layers/aspp.py:7-70): the statistics its four branch GCTs and its pooled branch share, the four gated copies of its input in
+// one pass, and the four GroupNorm + ReLU with the concatenation (and the plane norms of GCT(640)) in two.  Per element the expressions are
+// those of plane_reduce_kernel / plane_mean4_kernel, gct_gate_kernel, channel_scale_kernel, gn_stats_kernel and gn_apply_kernel.
+constexpr int AOC_PTR_LIST = 8;
+struct SrcList { const float *p[AOC_PTR_LIST]; };          // host arrays of device pointers travel in the kernel's argument struct
+struct DstList { float *p[AOC_PTR_LIST]; };
+
+// One pass over a plane: sum of x, sum of x^2 and the mean (aspp.py:19 via gct.py:19, four times, and aspp.py:46).  One workgroup per plane,
+// the traversal of plane_mean4_kernel (aligned float4 body, scalar head and tail, eight loads in flight); a fixed order, no atomics.
+__global__ __launch_bounds__(256) void plane_sum_sumsq_kernel(const float *__restrict__ x, int64_t hw, float *__restrict__ sum, float *__restrict__ sumsq,
+                                                               float *__restrict__ mean) {
+    __shared__ float wsum[2][4];
+    const float *xp = x + (size_t)blockIdx.x * hw;
+    const int64_t headn = floats_to_alignment(xp, hw);
+    const int64_t body4 = (hw - headn) / 4, tail0 = headn + body4 * 4;
+    const f32x4_t *x4 = reinterpret_cast<const f32x4_t *>(xp + headn);
+    float s = 0.0f, q = 0.0f;
+    if (threadIdx.x < headn) { const float v = xp[threadIdx.x]; s += v; q += v * v; }
+    if (threadIdx.x < hw - tail0) { const float v = xp[tail0 + threadIdx.x]; s += v; q += v * v; }
+    for (int64_t i0 = threadIdx.x; i0 < body4; i0 += 8 * 256) {
+        f32x4_t v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int64_t i = i0 + u * 256;
+            v[u] = __builtin_nontemporal_load(x4 + (i < body4 ? i : body4 - 1));
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            if (i0 + u * 256 < body4) {
+                s += (v[u].x + v[u].y) + (v[u].z + v[u].w);
+                q += (v[u].x * v[u].x + v[u].y * v[u].y) + (v[u].z * v[u].z + v[u].w * v[u].w);
+            }
+        }
+    }
+    s = aoc_wave_sum(s);
+    q = aoc_wave_sum(q);
+    if (aoc_lane() == 0) { wsum[0][threadIdx.x >> 6] = s; wsum[1][threadIdx.x >> 6] = q; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float ts = (wsum[0][0] + wsum[0][1]) + (wsum[0][2] + wsum[0][3]);
+        if (sum) sum[blockIdx.x] = ts;
+        if (sumsq) sumsq[blockIdx.x] = (wsum[1][0] + wsum[1][1]) + (wsum[1][2] + wsum[1][3]);
+        if (mean) mean[blockIdx.x] = ts / (float)hw;
+    }
+}
+
+// gct_gate_kernel for n_sets parameter sets over ONE [N, C] array of plane sums (aspp1..4.GCT read the same x): grid (N, n_sets), the body of
+// gct_gate_kernel on set blockIdx.y's alpha / gamma / beta, so each set carries the bits of aoc_gct_gate.  gate [n_sets, N, C].
+// The body is a COPY of gct_gate_kernel's, kept line for line, only because this kernel was added without touching the existing one: the two
+// belong in one __device__ routine called from both (test_gct_gate_multi_bits fails as soon as they drift apart).
+__global__ __launch_bounds__(256) void gct_gate_multi_kernel(const float *__restrict__ s, const float *__restrict__ alpha_all, const float *__restrict__ gamma_all,
+                                                              const float *__restrict__ beta_all, int C, float eps, int l1, float *__restrict__ gate_all) {
+    __shared__ float wsum[4];
+    __shared__ float mean_s;
+    const int n = blockIdx.x, N = gridDim.x;
+    const float *alpha = alpha_all + (size_t)blockIdx.y * C, *gamma = gamma_all + (size_t)blockIdx.y * C, *beta = beta_all + (size_t)blockIdx.y * C;
+    float *gate = gate_all + (size_t)blockIdx.y * N * C;
+    float part = 0.0f;
+    for (int c = threadIdx.x; c < C; c += blockDim.x) {
+        const float sv = s[(size_t)n * C + c];
+        const float e = l1 ? sv * alpha[c] : sqrtf(sv + eps) * alpha[c];
+        part += l1 ? fabsf(e) : e * e;
+    }
+    part = aoc_wave_sum(part);
+    if (aoc_lane() == 0) wsum[threadIdx.x >> 6] = part;
+    __syncthreads();
+    if (threadIdx.x == 0) mean_s = ((wsum[0] + wsum[1]) + (wsum[2] + wsum[3])) / (float)C;
+    __syncthreads();
+    const float m = mean_s;
+    for (int c = threadIdx.x; c < C; c += blockDim.x) {
+        const float sv = s[(size_t)n * C + c];
+        const float e = l1 ? sv * alpha[c] : sqrtf(sv + eps) * alpha[c];
+        const float norm = l1 ? gamma[c] / (m + eps) : gamma[c] / sqrtf(m + eps);
+        gate[(size_t)n * C + c] = 1.0f + tanhf(e * norm + beta[c]);
+    }
+}
+
+// y_k[p, :] = gains[k, p] * x[p, :] for k < n_out: x is read once for all its gated copies (aspp.py:19 via gct.py:36, four times).  grid.y =
+// plane; the plane is cut by y_0's alignment as in cat_film_scale_kernel and every access moves 16 bytes per lane through a type that promises
+// 4-byte alignment only, so neither x nor a y_k at another misalignment falls back to scalars.  y_0 may be x (n_out == 1): a thread stores
+// exactly the elements it loaded.  Four float4 per thread: with eight the compiler keeps the products of every output live (208 VGPRs).
+constexpr int CSM_U = 4;
+__global__ __launch_bounds__(256) void channel_scale_multi_kernel(const float *x, const float *__restrict__ gains, int n_out, int64_t planes, int64_t hw,
+                                                                   int chunk, DstList y) {
+    constexpr int U = CSM_U;
+    const int64_t plane = blockIdx.y;
+    const float *xp = x + plane * hw;
+    const int64_t headn = floats_to_alignment(y.p[0] + plane * hw, hw);
+    const int64_t body4 = (hw - headn) / 4;
+    const int64_t i0 = (int64_t)blockIdx.x * chunk, i1 = min(body4, i0 + chunk);          // chunk = ceil((hw / 4) / gridDim.x) <= 256 U
+    f32x4_t v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int64_t i = i0 + threadIdx.x + u * 256;
+        if (i < i1) v[u] = stream_load4(xp + headn + 4 * i);
+    }
+    const int64_t tail0 = headn + body4 * 4;
+    const int64_t e = threadIdx.x < headn ? threadIdx.x : tail0 + (threadIdx.x - headn);
+    const bool has_edge = blockIdx.x == 0 && e < hw && (threadIdx.x < headn || e >= tail0);
+    float edge = 0.0f;
+    if (has_edge) edge = xp[e];
+#pragma unroll
+    for (int k = 0; k < AOC_PTR_LIST; ++k) {
+        if (k < n_out) {
+            const float g = gains[(int64_t)k * planes + plane];
+            float *yp = y.p[k] + plane * hw;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int64_t i = i0 + threadIdx.x + u * 256;
+                if (i < i1) __builtin_nontemporal_store(v[u] * g, reinterpret_cast<f32x4_a4_t *>(yp + headn + 4 * i));
+            }
+            if (has_edge) yp[e] = g * edge;
+        }
+    }
+}
+
+// gn_stats_kernel over n_src tensors in one launch: grid (N * groups, n_src), the routine of gn_stats_kernel on source blockIdx.y
+// (per-thread fp32 partial sums of 8 folded in fp64, fixed order); stats [n_src][N * groups][2].  As above, the body is a line-for-line COPY
+// of gn_stats_kernel's for the same reason and should become one __device__ routine shared by both (test_groupnorm_cat_relu_bits_and_plane_sumsq
+// compares the bits of the two).
+__global__ __launch_bounds__(256) void gn_stats_multi_kernel(SrcList src, int group_channels, int64_t hw, float eps, float *__restrict__ stats_all) {
+    __shared__ double sh[2][4];
+    const float *x = src.p[0];
+#pragma unroll
+    for (int k = 1; k < AOC_PTR_LIST; ++k)
+        if ((int)blockIdx.y == k) x = src.p[k];
+    float *stats = stats_all + (size_t)blockIdx.y * gridDim.x * 2;
+    const float *xp = x + (size_t)blockIdx.x * group_channels * hw;
+    const int64_t n = (int64_t)group_channels * hw;
+    double s = 0.0, q = 0.0;
+    int64_t i = threadIdx.x;
+    for (; i + 7 * 256 < n; i += 8 * 256) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = xp[i + u * 256];
+        float ps = 0.f, pq = 0.f;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) { ps += v[u]; pq += v[u] * v[u]; }
+        s += ps; q += pq;
+    }
+    for (; i < n; i += 256) { const float v = xp[i]; s += v; q += (double)v * v; }
+    for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); q += __shfl_xor(q, o); }
+    if (aoc_lane() == 0) { sh[0][threadIdx.x >> 6] = s; sh[1][threadIdx.x >> 6] = q; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double ts = (sh[0][0] + sh[0][1]) + (sh[0][2] + sh[0][3]), tq = (sh[1][0] + sh[1][1]) + (sh[1][2] + sh[1][3]);
+        const double mean = ts / (double)n;
+        double var = tq / (double)n - mean * mean;
+        if (var < 0.0) var = 0.0;
+        stats[2 * blockIdx.x] = (float)mean;
+        stats[2 * blockIdx.x + 1] = (float)(1.0 / sqrt(var + (double)eps));
+    }
+}
+
+// The apply pass of n_src GroupNorms written straight into their concatenation (aspp.py:21-23 four times, :62-63): one workgroup per plane of
+// y [N, n_src C_src + C_tail, hw].  A plane of source k is [relu](x a + b) with gn_apply_kernel's a and b; a tail plane is the constant
+// [relu](tail[n, c]) (the pooled branch: bilinear interpolation from a 1 x 1 map with align_corners=True is a broadcast).  The plane is cut by
+// y's alignment, sources are loaded 16 bytes per lane at any misalignment.  plane_sumsq (optional) = the sum over the plane of the squares of
+// the values being stored (what GCT(640) would read the concatenation for, aspp.py:65), in a fixed order.
+template <int U>
+__global__ __launch_bounds__(256) void gn_cat_apply_kernel(SrcList src, int n_src, int N, int C_src, int group_channels, int64_t hw,
+                                                            const float *__restrict__ stats, const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                            const float *__restrict__ tail, int C_tail, int relu, float *__restrict__ y,
+                                                            float *__restrict__ plane_sumsq) {
+    __shared__ float wsum[4];
+    const int C_total = n_src * C_src + C_tail;
+    const int64_t plane = blockIdx.x;
+    const int n = (int)(plane / C_total), cc = (int)(plane - (int64_t)n * C_total);
+    float *yp = y + plane * hw;
+    const int64_t headn = floats_to_alignment(yp, hw);
+    const int64_t body4 = (hw - headn) / 4, tail0 = headn + body4 * 4;
+    const int64_t e = threadIdx.x < headn ? threadIdx.x : tail0 + (threadIdx.x - headn);
+    const bool has_edge = e < hw && (threadIdx.x < headn || e >= tail0);
+    float acc = 0.0f;
+    if (cc < n_src * C_src) {
+        const int k = cc / C_src, c = cc - k * C_src;
+        const float *xk = src.p[0];
+#pragma unroll
+        for (int j = 1; j < AOC_PTR_LIST; ++j)
+            if (k == j) xk = src.p[j];
+        const int groups = C_src / group_channels;
+        const int g = (k * N + n) * groups + c / group_channels;
+        const float mean = stats[2 * g], rstd = stats[2 * g + 1];
+        const float a = rstd * (gamma ? gamma[cc] : 1.0f), b = (beta ? beta[cc] : 0.0f) - mean * a;
+        const float *xp = xk + ((size_t)n * C_src + c) * hw;
+        if (has_edge) {
+            float t = xp[e] * a + b;
+            if (relu) t = fmaxf(t, 0.0f);
+            yp[e] = t;
+            acc += t * t;
+        }
+        for (int64_t i0 = threadIdx.x; i0 < body4; i0 += U * 256) {
+            f32x4_t v[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int64_t i = i0 + u * 256;
+                v[u] = stream_load4(xp + headn + 4 * (i < body4 ? i : body4 - 1));
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int64_t i = i0 + u * 256;
+                if (i < body4) {
+                    f32x4_t t = v[u] * a + b;
+                    if (relu) { t.x = fmaxf(t.x, 0.0f); t.y = fmaxf(t.y, 0.0f); t.z = fmaxf(t.z, 0.0f); t.w = fmaxf(t.w, 0.0f); }
+                    __builtin_nontemporal_store(t, reinterpret_cast<f32x4_t *>(yp + headn + 4 * i));
+                    acc += (t.x * t.x + t.y * t.y) + (t.z * t.z + t.w * t.w);
+                }
+            }
+        }
+    } else {
+        float t = tail[(size_t)n * C_tail + (cc - n_src * C_src)];
+        if (relu) t = fmaxf(t, 0.0f);
+        const f32x4_t t4 = {t, t, t, t};
+        if (has_edge) { yp[e] = t; acc += t * t; }
+        for (int64_t i = threadIdx.x; i < body4; i += 256) {
+            __builtin_nontemporal_store(t4, reinterpret_cast<f32x4_t *>(yp + headn + 4 * i));
+            acc += (t * t + t * t) + (t * t + t * t);
+        }
+    }
+    if (plane_sumsq) {
+        acc = aoc_wave_sum(acc);
+        if (aoc_lane() == 0) wsum[threadIdx.x >> 6] = acc;
+        __syncthreads();
+        if (threadIdx.x == 0) plane_sumsq[plane] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    }
+}
+
+// [a, a + na) and [b, b + nb) floats share an element
+inline bool ranges_overlap(const float *a, int64_t na, const float *b, int64_t nb) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + (uintptr_t)nb * sizeof(float) && b0 < a0 + (uintptr_t)na * sizeof(float);
+}
+
 inline int pool_chunks(int64_t hw) { return (int)((hw + MP_PIX - 1) / MP_PIX); }
 
 }  // namespace
@@ -1511,6 +1745,102 @@ int aoc_object_logit(const float *x, int N, int C, int64_t hw, const float *weig
     if (N > 65535) return AOC_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(object_logit_kernel, dim3((unsigned)((hw + 255) / 256), N), dim3(256), 0, aoc_hip_stream(stream), x, C, hw, weight, weight_stride,
                        bias, bias_stride, out);
+    AOC_RETURN_IF_LAUNCH_FAILED();
+    return AOC_OK;
+}
+
+int aoc_plane_sum_sumsq(const float *x, int64_t planes, int64_t hw, float *sum, float *sumsq, float *mean, aoc_stream_t stream) {
+    if (!x || planes < 1 || hw < 1 || (!sum && !sumsq && !mean)) return AOC_ERR_INVALID_ARG;
+    if (planes > 2147483647ll) return AOC_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(plane_sum_sumsq_kernel, dim3((unsigned)planes), dim3(256), 0, aoc_hip_stream(stream), x, hw, sum, sumsq, mean);
+    AOC_RETURN_IF_LAUNCH_FAILED();
+    return AOC_OK;
+}
+
+int aoc_gct_gate_multi(const float *plane_sums, const float *alpha, const float *gamma, const float *beta, int n_sets, int N, int C, float eps,
+                       int l1_mode, float *gate, aoc_stream_t stream) {
+    if (!plane_sums || !alpha || !gamma || !beta || !gate || n_sets < 1 || N < 1 || C < 1) return AOC_ERR_INVALID_ARG;
+    if (n_sets > 65535) return AOC_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(gct_gate_multi_kernel, dim3((unsigned)N, (unsigned)n_sets), dim3(256), 0, aoc_hip_stream(stream), plane_sums, alpha, gamma, beta, C, eps,
+                       l1_mode, gate);
+    AOC_RETURN_IF_LAUNCH_FAILED();
+    return AOC_OK;
+}
+
+int aoc_channel_scale_multi(const float *x, const float *gains, int n_out, int64_t planes, int64_t hw, float *const *y_ptrs, aoc_stream_t stream) {
+    if (!x || !gains || !y_ptrs || n_out < 1 || n_out > AOC_PTR_LIST || planes < 1 || hw < 1) return AOC_ERR_INVALID_ARG;
+    if (planes > 65535) return AOC_ERR_UNSUPPORTED;
+    if (hw > INT64_MAX / 4 / planes) return AOC_ERR_UNSUPPORTED;
+    const int64_t n = planes * hw;
+    DstList dst = {};
+    for (int k = 0; k < n_out; ++k) {
+        float *yk = y_ptrs[k];
+        if (!yk) return AOC_ERR_INVALID_ARG;
+        // in place only as the single output; every other overlap with x or between two outputs is rejected
+        if (!(n_out == 1 && yk == x) && ranges_overlap(yk, n, x, n)) return AOC_ERR_INVALID_ARG;
+        for (int j = 0; j < k; ++j)
+            if (ranges_overlap(yk, n, y_ptrs[j], n)) return AOC_ERR_INVALID_ARG;
+        dst.p[k] = yk;
+    }
+    const int64_t per_wg = 256 * (int64_t)CSM_U;
+    const unsigned gx = (unsigned)std::max<int64_t>(1, (hw / 4 + per_wg - 1) / per_wg);
+    const int chunk = (int)std::max<int64_t>(1, (hw / 4 + gx - 1) / gx);
+    hipLaunchKernelGGL(channel_scale_multi_kernel, dim3(gx, (unsigned)planes), dim3(256), 0, aoc_hip_stream(stream), x, gains, n_out, planes, hw, chunk, dst);
+    AOC_RETURN_IF_LAUNCH_FAILED();
+    return AOC_OK;
+}
+
+size_t aoc_groupnorm_cat_relu_workspace_bytes(int n_src, int N, int groups) {
+    return n_src < 1 || n_src > AOC_PTR_LIST || N < 1 || groups < 1 ? 0 : aoc_align_up((size_t)n_src * N * groups * 2 * sizeof(float), 256);
+}
+
+int aoc_groupnorm_cat_relu(const float *const *x_ptrs, int n_src, int N, int C_src, int64_t hw, int groups, const float *gamma, const float *beta, float eps,
+                           const float *tail, int C_tail, int relu, float *y, float *plane_sumsq, void *workspace, size_t workspace_bytes,
+                           aoc_stream_t stream) {
+    if (!x_ptrs || !y || !workspace || n_src < 1 || n_src > AOC_PTR_LIST || N < 1 || C_src < 1 || hw < 1 || groups < 1 || C_tail < 0)
+        return AOC_ERR_INVALID_ARG;
+    if (C_src % groups) return AOC_ERR_INVALID_ARG;
+    if (C_tail > 0 && !tail) return AOC_ERR_INVALID_ARG;
+    const int64_t C_total = (int64_t)n_src * C_src + C_tail;
+    if (C_total > 2147483647ll || (int64_t)N * C_total > 2147483647ll || (int64_t)N * groups > 2147483647ll) return AOC_ERR_UNSUPPORTED;
+    if (hw > INT64_MAX / 4 / ((int64_t)N * C_total)) return AOC_ERR_UNSUPPORTED;
+    const int64_t ny = (int64_t)N * C_total * hw, nx = (int64_t)N * C_src * hw;
+    SrcList src = {};
+    for (int k = 0; k < n_src; ++k) {
+        if (!x_ptrs[k]) return AOC_ERR_INVALID_ARG;
+        if (ranges_overlap(y, ny, x_ptrs[k], nx)) return AOC_ERR_INVALID_ARG;              // y aliases no input
+        src.p[k] = x_ptrs[k];
+    }
+    if (C_tail > 0 && ranges_overlap(y, ny, tail, (int64_t)N * C_tail)) return AOC_ERR_INVALID_ARG;
+    const int64_t n_affine = (int64_t)n_src * C_src, n_stats = (int64_t)n_src * N * groups * 2, n_sq = (int64_t)N * C_total;
+    const float *ws = static_cast<const float *>(workspace);
+    if ((gamma && ranges_overlap(y, ny, gamma, n_affine)) || (beta && ranges_overlap(y, ny, beta, n_affine)) || ranges_overlap(y, ny, ws, n_stats))
+        return AOC_ERR_INVALID_ARG;
+    if (plane_sumsq) {                                                                      // the second output overlaps nothing either
+        if (ranges_overlap(plane_sumsq, n_sq, y, ny) || ranges_overlap(plane_sumsq, n_sq, ws, n_stats)) return AOC_ERR_INVALID_ARG;
+        if ((gamma && ranges_overlap(plane_sumsq, n_sq, gamma, n_affine)) || (beta && ranges_overlap(plane_sumsq, n_sq, beta, n_affine)))
+            return AOC_ERR_INVALID_ARG;
+        if (C_tail > 0 && ranges_overlap(plane_sumsq, n_sq, tail, (int64_t)N * C_tail)) return AOC_ERR_INVALID_ARG;
+        for (int k = 0; k < n_src; ++k)
+            if (ranges_overlap(plane_sumsq, n_sq, x_ptrs[k], nx)) return AOC_ERR_INVALID_ARG;
+    }
+    for (int k = 0; k < n_src; ++k)                                                         // nor do the statistics land in anything that is read
+        if (ranges_overlap(ws, n_stats, x_ptrs[k], nx)) return AOC_ERR_INVALID_ARG;
+    if ((gamma && ranges_overlap(ws, n_stats, gamma, n_affine)) || (beta && ranges_overlap(ws, n_stats, beta, n_affine)) ||
+        (C_tail > 0 && ranges_overlap(ws, n_stats, tail, (int64_t)N * C_tail)))
+        return AOC_ERR_INVALID_ARG;
+    if (workspace_bytes < aoc_groupnorm_cat_relu_workspace_bytes(n_src, N, groups)) return AOC_ERR_WORKSPACE;
+    hipStream_t st = aoc_hip_stream(stream);
+    float *stats = static_cast<float *>(workspace);
+    hipLaunchKernelGGL(gn_stats_multi_kernel, dim3((unsigned)(N * groups), (unsigned)n_src), dim3(256), 0, st, src, C_src / groups, hw, eps, stats);
+    AOC_RETURN_IF_LAUNCH_FAILED();
+    const dim3 grid((unsigned)(N * C_total));
+    if (hw / 4 <= 1024)
+        hipLaunchKernelGGL(gn_cat_apply_kernel<4>, grid, dim3(256), 0, st, src, n_src, N, C_src, C_src / groups, hw, stats, gamma, beta, tail, C_tail, relu, y,
+                           plane_sumsq);
+    else
+        hipLaunchKernelGGL(gn_cat_apply_kernel<8>, grid, dim3(256), 0, st, src, n_src, N, C_src, C_src / groups, hw, stats, gamma, beta, tail, C_tail, relu, y,
+                           plane_sumsq);
     AOC_RETURN_IF_LAUNCH_FAILED();
     return AOC_OK;
 }

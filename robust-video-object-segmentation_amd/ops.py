@@ -1147,6 +1147,114 @@ def gct_gate(plane_sums, alpha, gamma, beta, eps, l1_mode=False):
     return gate
 
 
+# ------------------------------------------------------------------------------------------ ASPP (networks/layers/aspp.py)
+def plane_sum_sumsq(x, want_sum=True, want_sumsq=True, want_mean=True):
+    """x [N, C, H, W] -> (sum, sumsq, mean), each [N, C] or None where not wanted, from ONE pass over x (aspp.py:19 via gct.py:19, and :46)."""
+    if x.dim() < 2:
+        raise ValueError(f"plane_sum_sumsq: x {tuple(x.shape)} has no [N, C] planes")
+    if not (want_sum or want_sumsq or want_mean):
+        raise ValueError("plane_sum_sumsq: no output wanted")
+    x = _f32c(x)
+    _need_gpu(x)
+    N, C = x.shape[0], x.shape[1]
+    hw = x.numel() // (N * C)
+    new = lambda want: torch.empty(N, C, dtype=torch.float32, device=x.device) if want else None
+    s, q, m = new(want_sum), new(want_sumsq), new(want_mean)
+    _lib.check(_lib.lib().aoc_plane_sum_sumsq(_p(x), N * C, hw, _p(s), _p(q), _p(m), _stream()), "aoc_plane_sum_sumsq")
+    return s, q, m
+
+
+def _gct_rows(what, params, C):
+    """A list of per-set parameters ([1, C, 1, 1] or [C]) or one [n_sets, C] tensor -> a contiguous float32 [n_sets, C]."""
+    rows = params if torch.is_tensor(params) else torch.stack([p.reshape(-1) for p in params])
+    if rows.dim() != 2 or rows.shape[1] != C:
+        raise ValueError(f"{what}: parameters {tuple(rows.shape)} do not fit {C} channels")
+    return _f32c(rows)
+
+
+def gct_gate_multi(plane_sums, alpha, gamma, beta, eps, l1_mode=False):
+    """aoc_gct_gate_multi: the gates of several GCTs that read the same tensor.  alpha, gamma, beta: [n_sets, C] tensors or lists of n_sets
+    per-GCT parameters; returns gate [n_sets, N, C], set k bit-equal to ``gct_gate(plane_sums, alpha[k], gamma[k], beta[k], eps, l1_mode)``."""
+    if plane_sums.dim() != 2:
+        raise ValueError(f"gct_gate_multi: plane sums {tuple(plane_sums.shape)} are not [N, C]")
+    N, C = plane_sums.shape
+    al, ga, be = (_gct_rows("gct_gate_multi", p, C) for p in (alpha, gamma, beta))          # bound until the launch is enqueued
+    if not (al.shape[0] == ga.shape[0] == be.shape[0]) or al.shape[0] < 1:
+        raise ValueError(f"gct_gate_multi: {al.shape[0]} alpha, {ga.shape[0]} gamma and {be.shape[0]} beta sets")
+    plane_sums = _f32c(plane_sums)
+    _need_gpu(plane_sums, al, ga, be)
+    n_sets = al.shape[0]
+    gate = torch.empty(n_sets, N, C, dtype=torch.float32, device=plane_sums.device)
+    _lib.check(_lib.lib().aoc_gct_gate_multi(_p(plane_sums), _p(al), _p(ga), _p(be), n_sets, N, C, float(eps), int(bool(l1_mode)), _p(gate), _stream()),
+               "aoc_gct_gate_multi")
+    return gate
+
+
+def _ptr_array(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def channel_scale_multi(x, gains, outs=None):
+    """aoc_channel_scale_multi: [gains[k][:, :, None, None] * x for k] with x read once.  gains [n_out, N, C] (n_out <= 8); outs: optional list
+    of n_out contiguous float32 tensors shaped like x (outs[0] may be x itself when n_out == 1).  Each result is bit-equal to channel_scale."""
+    if x.dim() < 2 or gains.dim() != 3 or tuple(gains.shape[1:]) != tuple(x.shape[:2]):
+        raise ValueError(f"channel_scale_multi: gains {tuple(gains.shape)} do not fit x {tuple(x.shape)}")
+    n_out = gains.shape[0]
+    if not 1 <= n_out <= 8:
+        raise ValueError(f"channel_scale_multi: {n_out} outputs (1 to 8)")
+    if outs is not None and (len(outs) != n_out or any(tuple(o.shape) != tuple(x.shape) or o.dtype != torch.float32 or not o.is_contiguous() for o in outs)):
+        raise ValueError(f"channel_scale_multi: outs must be {n_out} contiguous float32 tensors of shape {tuple(x.shape)}")
+    x, gains = _f32c(x), _f32c(gains)
+    _need_gpu(x, gains, *(outs or ()))
+    planes = x.shape[0] * x.shape[1]
+    hw = x.numel() // planes
+    ys = [torch.empty_like(x) for _ in range(n_out)] if outs is None else list(outs)
+    _lib.check(_lib.lib().aoc_channel_scale_multi(_p(x), _p(gains), n_out, planes, hw, _ptr_array(ys), _stream()), "aoc_channel_scale_multi")
+    return ys
+
+
+def groupnorm_cat_relu(xs, groups, gamma, beta, eps=1e-5, tail=None, relu=True, want_plane_sumsq=False, out=None):
+    """aoc_groupnorm_cat_relu: ``torch.cat([groupnorm_relu(x_k, groups, gamma[k], beta[k], eps, None, relu) for k] + [tail expanded], 1)`` (bit-equal)
+    in a statistics launch and an apply launch (aspp.py:21-23 x 4, :62-63).  xs: 1 to 8 tensors [N, C_src, H, W]; gamma, beta: [n_src, C_src],
+    lists of n_src [C_src] tensors, or None; tail [N, C_tail] or [N, C_tail, 1, 1] (relu applies to it too) or None.  With want_plane_sumsq
+    also returns the plane sums of squares [N, C_total] of the result (what GCT's l2 mode reads it for)."""
+    xs = list(xs)
+    n_src = len(xs)
+    if not 1 <= n_src <= 8:
+        raise ValueError(f"groupnorm_cat_relu: {n_src} sources (1 to 8)")
+    if any(x.dim() < 2 or tuple(x.shape) != tuple(xs[0].shape) for x in xs):
+        raise ValueError(f"groupnorm_cat_relu: the sources differ in shape: {[tuple(x.shape) for x in xs]}")
+    N, C = xs[0].shape[0], xs[0].shape[1]
+    if int(groups) < 1 or C % int(groups):
+        raise ValueError(f"groupnorm_cat_relu: {C} channels do not divide into {groups} groups")
+    g = b = None
+    if gamma is not None:
+        g = _gct_rows("groupnorm_cat_relu", gamma, C)                   # converted copies stay bound until the launch is enqueued
+    if beta is not None:
+        b = _gct_rows("groupnorm_cat_relu", beta, C)
+    if any(t is not None and t.shape[0] != n_src for t in (g, b)):
+        raise ValueError(f"groupnorm_cat_relu: {n_src} sources, affine parameters for {[t.shape[0] for t in (g, b) if t is not None]}")
+    C_tail = 0
+    if tail is not None:
+        if tail.dim() < 2 or tail.shape[0] != N or tail.numel() != N * tail.shape[1]:
+            raise ValueError(f"groupnorm_cat_relu: the tail {tuple(tail.shape)} is not [N = {N}, C_tail] (or [N, C_tail, 1, 1])")
+        C_tail = tail.shape[1]
+        tail = _f32c(tail)
+    xs = [_f32c(x) for x in xs]
+    shape = (N, n_src * C + C_tail) + tuple(xs[0].shape[2:])
+    if out is not None and (tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous()):
+        raise ValueError(f"groupnorm_cat_relu: out must be a contiguous float32 tensor of shape {shape}")
+    _need_gpu(*xs, g, b, tail, out)
+    hw = xs[0].numel() // (N * C)
+    L = _lib.lib()
+    y = torch.empty(shape, dtype=torch.float32, device=xs[0].device) if out is None else out
+    sq = torch.empty(N, shape[1], dtype=torch.float32, device=y.device) if want_plane_sumsq else None
+    ws = _ws(L.aoc_groupnorm_cat_relu_workspace_bytes(n_src, N, int(groups)), y.device)
+    _lib.check(L.aoc_groupnorm_cat_relu(_ptr_array(xs), n_src, N, C, hw, int(groups), _p(g), _p(b), float(eps), _p(tail), C_tail, int(bool(relu)),
+                                        _p(y), _p(sq), _p(ws), ws.numel(), _stream()), "aoc_groupnorm_cat_relu")
+    return (y, sq) if want_plane_sumsq else y
+
+
 def object_logit(x, weight_bias):
     """x [N, C, H, W], weight_bias [N, C + 1] (weights then bias, decoding_module.py:154-156) -> [N, 1, H, W]."""
     x = _f32c(x)
