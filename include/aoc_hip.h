@@ -177,8 +177,9 @@ int aoc_build_proxies(const float *pool, int64_t pool_rows, int C, const int32_t
  *  sets         HOST arrays of length n_set: set s = proxies[set_begin[s] .. set_begin[s] + set_size[s]);
  *               value = min over the set; an empty or all-ignored set yields AOC_PAD_DISTANCE
  *               (reference: absent object, AEM:310-313).  Single-proxy sets are the k = 1 proxies
- *               (no min).  The set structure is static (kmax slots per object; unused slots carry
- *               norm = +inf), so the host knows it without a device round trip.
+ *               (no min; one whose norm is +inf is an all-ignored set like any other).  The set
+ *               structure is static (kmax slots per object; unused slots carry norm = +inf), so the
+ *               host knows it without a device round trip.
  *  set_bias     [n_set] device (dis_bias of the set's object); may be NULL (= 0)
  *  out element (pixel i, set s) is written at out[i * out_pixel_stride + set_out_offset[s]], so a set
  *               can land in its channel of the [O, 24, h, w] proto-mask buffer or in [1,h,w,O,F].
@@ -208,8 +209,10 @@ int aoc_proxy_corr_min_f16(const float *query, int64_t m, int C,
  *
  *  precision AOC_CORR_SPLIT (C = 100 only; other widths run the fp32 kernel): every value x 2^10 is split in registers into hi + lo
  *            fp16 and q.p = qh.ph + qh.pl + ql.ph (dropped ql.pl term < 2^-22 |q.p|) is accumulated in fp32 by
- *            v_mfma_f32_32x32x16_f16 as ONE K = 304 dot product that also carries -|p|^2/2; fp32-equivalent (tests pin <= 5e-6 on the
- *            outputs).  Needs |x| 2^10 <= 65000 and |x|^2 <= 4000 for every query / proxy value; checked on the device, and when it
+ *            v_mfma_f32_32x32x16_f16 as ONE K = 304 dot product that also carries -|p|^2/2; fp32-equivalent: tests/test_gpu_global_match.py
+ *            holds raw and transformed outputs to a float64 reference under a bound that evaluates the split of every operand and
+ *            adds gamma(337) for the accumulation (tests/global_match_bounds.py: about 1e-5 on distances of O(1)).
+ *            Needs |x| 2^10 <= 65000 and |x|^2 <= 4000 for every query / proxy value; checked on the device, and when it
  *            fails the exact-fp32 kernel recomputes the launch inside the same call (no host round trip).
  *  precision AOC_CORR_FP32: exact fp32 MFMA (v_mfma_f32_16x16x4_f32), the arithmetic of aoc_proxy_corr_min.
  *  workspace: aoc_proxy_corr_min_batched_workspace_bytes() bytes (the device-side take-over flag: the kernel stores the call's sequence
@@ -295,7 +298,9 @@ int aoc_dense_match_min_f16(const float *query, int64_t m, int C,
  * spare k-slots (and, in a fourth one, an upper bound of the norm of the row's lo plane).  q.r is then qh.rh + qh.rl + ql.rh
  * accumulated in fp32 by v_mfma_f32_32x32x16_f16 (the dropped ql.rl term is < 2^-22 |q| |r|): a product carries up to about 4x the
  * rounding error of an fp32 product, and the deviations of the min-distances from the fp32 reference stay within a small multiple
- * of the reference's own fp32 rounding (a few 1e-7 on distances of O(1); tests pin <= 5e-6 on the outputs).
+ * of the reference's own fp32 rounding (a few 1e-7 on distances of O(1)).  tests/test_gpu_global_match.py holds raw and transformed
+ * outputs to a float64 reference under a bound that evaluates the split of every operand and the norm pieces and adds gamma(337) for the
+ * accumulation (tests/global_match_bounds.py: about 2e-5 on distances of O(1)).
  *
  * The kernel evaluates the qh.rh product for every (32 reference pixels x 32 query pixels) pair and the two cross products only for
  * the pairs that can hold a minimum: |qh.rl + ql.rh| <= |qh||rl| + |ql||rh| (plane norms from the records), so a pair whose one-product

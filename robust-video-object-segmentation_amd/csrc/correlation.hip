@@ -212,6 +212,9 @@ __global__ __launch_bounds__(256) void proxy_corr_min_kernel(PcFrames frames, in
             for (int r = 0; r < 4; ++r)   // AEM:43; in float16 mode every tensor-level result is a float16
                 d[r] = F16 ? aoc_h(aoc_h(q2r[r] + t.p2) - 2.0f * aoc_h(acc[r])) : (q2r[r] + t.p2) - 2.0f * acc[r];
             if (pt.flags & 1) {   // column-wise: k = 1 proxies, no min (AEM:127)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (d[r] == INFINITY) d[r] = AOC_PAD_DISTANCE;        // absent k = 1 proxy (norm = +inf): the constant of AEM:310-313, as the min path
                 if (j < pt.ncols) {
                     if (nout > 0) {
 #pragma unroll
@@ -608,6 +611,9 @@ int aoc_corr_fp32_batched(const aoc_corr_frame *frames_host, int n_frames, int64
     int max_tiles = (int)((size_t)130 * 1024 / tile_bytes);   // leaves room for the per-wave transpose buffer
     if (max_tiles > PC_MAX_TILES) max_tiles = PC_MAX_TILES;
     if (max_tiles < 4) return AOC_ERR_UNSUPPORTED;
+    // a set whose proxies do not fit the LDS image of one launch is rejected before anything is enqueued (as cb_run does)
+    for (int s = 0; s < n_set; ++s)
+        if ((set_size_host[s] + 15) / 16 > max_tiles) return AOC_ERR_UNSUPPORTED;
     const int64_t n_row_tiles = (m + 15) / 16;
     int grid = (int)((n_row_tiles + 3) / 4);
     if (grid > 512) grid = 512;        // two blocks per CU (LDS permitting): tiles staged once per block, waves walk the row tiles
@@ -660,7 +666,6 @@ int aoc_corr_fp32_batched(const aoc_corr_frame *frames_host, int n_frames, int64
                 s += run;
             } else {
                 const int nt = size == 0 ? 1 : (size + 15) / 16;
-                if (nt > max_tiles) return AOC_ERR_UNSUPPORTED;
                 if (tab.n + nt > max_tiles) { int rc = flush(); if (rc) return rc; }
                 const int oc0 = add_out(set_out_offset_host[s], s);
                 for (int t = 0; t < nt; ++t) {

@@ -39,7 +39,7 @@ def _widen(a, f16):
     return a.astype(np.float64)
 
 
-def pair_distances(query, prev, f16=False, channels=None):
+def pair_distances(query, prev, f16=False, channels=None, e_p2=None):
     """D[i, j] = |q_i - p_j|^2 written as the kernels write it, (|q_i|^2 + |p_j|^2) - 2 q_i.p_j, in float64 over all pairs of pixels, and
     E[i, j], the bound on |kernel's float32 value - D[i, j]|.  query, prev [H, W, C] float32 (rounded to float16 first in f16 mode: the
     value the kernel works on).
@@ -54,7 +54,9 @@ def pair_distances(query, prev, f16=False, channels=None):
     float16 mode.  Every aoc_h(x) is one more rounding of a float32 value to float16: x (1 + UH) + SUBH at most (SUBH covers the subnormal
     range, squares below 2^-14).  The squares are rounded (aoc_h(v v), the float32 product of two float16 values is exact), added in float32
     (gamma(C) as above) and the sum is rounded; the accumulator of the matrix instruction is rounded once; aoc_h(q2 + y2) is a float32
-    addition and a rounding; so is the final aoc_h(. - 2 aoc_h(acc)).  Magnitudes are O(1), far from 65504."""
+    addition and a rounding; so is the final aoc_h(. - 2 aoc_h(acc)).  Magnitudes are O(1), far from 65504.
+    e_p2 [pixels of prev]: the error of the candidates' norms where the kernel does not compute them itself (a caller-supplied float32 norm:
+    global_match_bounds.py); it replaces the derived one."""
     q = _widen(query, f16).reshape(-1, query.shape[-1])
     p = _widen(prev, f16).reshape(-1, prev.shape[-1])
     if channels is not None:
@@ -73,7 +75,7 @@ def pair_distances(query, prev, f16=False, channels=None):
         e = e + g * (n2 + e)                         # their float32 sum
         return e + UH * (n2 + e) + SUBH              # aoc_h of the sum
 
-    e_q2, e_p2 = norm_err(q2), norm_err(p2)
+    e_q2, e_p2 = norm_err(q2), norm_err(p2) if e_p2 is None else np.asarray(e_p2, np.float64)
     e_dot = g * adot
     if f16:
         e_dot = e_dot + UH * (np.abs(dot) + e_dot) + SUBH
