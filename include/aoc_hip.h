@@ -292,6 +292,52 @@ int aoc_dense_match_min_f16(const float *query, int64_t m, int C,
                             int transform, void *workspace, size_t workspace_bytes, aoc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Training-time global matching (csrc/match_grad.hip): what autograd needs of global_matching (AEM:616-685 over AEM:178-227, 61-89) and
+ * global_matching_proxy (AEM:336-402 over AEM:112-175) without the [m, O, n] distance tensor the reference keeps for its backward.
+ * fp32 only.  With d = |q|^2 + |r|^2 - 2 q.r and T = 2 sigmoid(d + b) - 1:  dT/dd = dT/db = (1 - T^2) / 2, dd/dq = 2 (q - r*),
+ * dd/dr* = 2 (r* - q), r* the row of the minimum (AEM:88 torch.min; the lowest row on ties).
+ *
+ * aoc_dense_match_argmin: aoc_dense_match_min (AEM:178-227 + 61-89, transform AEM:676) that also reports the minimiser.  Same arguments
+ * plus arg, int32, addressed like out: arg[i*out_pixel_stride + o*out_obj_stride] = the POOL ROW (not the position in fg_rows) of the
+ * minimum; ties go to the lowest pool row; -1 where the winning distance is a padded one (>= AOC_PAD_DISTANCE / 2: no right row) and
+ * when *n_fg == 0 -- T is exactly 1.0f there and the gradient zero.  out holds bit for bit the values of aoc_dense_match_min (the same
+ * tile routine; an index rides beside each minimum).  1 .. AOC_MAX_OBJECTS objects, C as aoc_dense_match_min. */
+size_t aoc_dense_match_argmin_workspace_bytes(int64_t m, int64_t n_fg_capacity, int n_obj);
+int aoc_dense_match_argmin(const float *query, int64_t m, int C,
+                           const float *pool, const int32_t *fg_rows, const int32_t *n_fg,
+                           int64_t n_fg_capacity, const uint32_t *wrong_bits,
+                           const float *obj_bias, int n_obj,
+                           float *out, int32_t *arg, int64_t out_pixel_stride, int64_t out_obj_stride,
+                           int transform, void *workspace, size_t workspace_bytes, aoc_stream_t stream);
+
+/* The backward of AEM:671-676 (min over the padded distances, proto-mask transform).  grad_out, T (the saved transformed output) and arg
+ * (aoc_dense_match_argmin's) are addressed as [i*pixel_stride + o*obj_stride]; query [m, C]; pool [n, C], all n rows.
+ *   g[i,o] = grad_out * 0.5 * (1 - T*T)
+ *   grad_query [m, C]  = sum_o g * 2 (q_i - pool[arg])                     (pairs with arg < 0 or >= n contribute nothing)
+ *   grad_pool  [n, C]  = sum over the pairs that chose the row of g * 2 (pool[r] - q_i); every row is written, rows nobody chose with zeros
+ *   grad_bias  [n_obj] = sum_i g
+ * Each output may be NULL (not wanted; nothing is written or computed for it).  Deterministic: no float atomics; every sum is added in a
+ * fixed order (ascending pixel, then object; long lists over a fixed tree of pair-id ranges), so the same buffers give the same bits.
+ * C <= AOC_MAX_CHANNELS, n_obj <= AOC_MAX_OBJECTS. */
+size_t aoc_dense_match_grad_workspace_bytes(int64_t m, int64_t n, int C, int n_obj);
+int aoc_dense_match_grad(const float *grad_out, const float *T, const int32_t *arg, int64_t pixel_stride, int64_t obj_stride,
+                         const float *query, int64_t m, int C, const float *pool, int64_t n, int n_obj,
+                         float *grad_query, float *grad_pool, float *grad_bias,
+                         void *workspace, size_t workspace_bytes, aoc_stream_t stream);
+
+/* The backward of the k = 1 proxy path (AEM:388-393: one distance per object, no min): the forward is aoc_proxy_corr_min with
+ * single-proxy sets and transform = 1.  proxies [n_obj, C]; g as above;
+ *   grad_query [m, C]       = sum_o g * 2 (q_i - p_o)
+ *   grad_proxies [n_obj, C] = 2 (p_o sum_i g - sum_i g q_i)                (a two-stage reduction over the pixels in a fixed order)
+ *   grad_bias [n_obj]       = sum_i g
+ * Each output may be NULL.  Deterministic like aoc_dense_match_grad. */
+size_t aoc_proxy_match_grad_workspace_bytes(int64_t m, int C, int n_obj);
+int aoc_proxy_match_grad(const float *grad_out, const float *T, int64_t pixel_stride, int64_t obj_stride,
+                         const float *query, int64_t m, int C, const float *proxies, int n_obj,
+                         float *grad_query, float *grad_proxies, float *grad_bias,
+                         void *workspace, size_t workspace_bytes, aoc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Dense pixel-level matching on the fp16 matrix pipe with fp32-equivalent products (same reference
  * lines as aoc_dense_match_min).  Each embedding row is converted ONCE into a "split record":
  * x * 2^10 = hi + lo with hi, lo fp16 (two 11-bit significands: |error| <= 2^-22 |x|, typically 2^-23), plus the three fp16 pieces of -16 |x|^2 in

@@ -119,6 +119,12 @@ SIGNATURES = {
     "aoc_channel_scale_multi": (_i, [_vp, _vp, _i, _i64, _i64, _vp, _vp]),
     "aoc_groupnorm_cat_relu_workspace_bytes": (_sz, [_i, _i, _i]),
     "aoc_groupnorm_cat_relu": (_i, [_vp, _i, _i, _i, _i64, _i, _vp, _vp, _f, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "aoc_dense_match_argmin_workspace_bytes": (_sz, [_i64, _i64, _i]),
+    "aoc_dense_match_argmin": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _i64, _i64, _i, _vp, _sz, _vp]),
+    "aoc_dense_match_grad_workspace_bytes": (_sz, [_i64, _i64, _i, _i]),
+    "aoc_dense_match_grad": (_i, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _i, _vp, _i64, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "aoc_proxy_match_grad_workspace_bytes": (_sz, [_i64, _i, _i]),
+    "aoc_proxy_match_grad": (_i, [_vp, _vp, _i64, _i64, _vp, _i64, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 STATUS = {0: "AOC_OK", -1: "AOC_ERR_INVALID_ARG", -2: "AOC_ERR_WORKSPACE", -3: "AOC_ERR_LAUNCH", -4: "AOC_ERR_UNSUPPORTED"}

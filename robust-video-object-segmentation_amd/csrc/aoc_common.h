@@ -67,6 +67,13 @@ int aoc_dense_match_min_gated(const float *query, int64_t m, int C, const float 
                               int64_t out_pixel_stride, int64_t out_obj_stride, int transform, void *workspace, size_t workspace_bytes,
                               const int32_t *gate, aoc_stream_t stream, int float16 = 0);
 
+// The launches behind aoc_dense_match_argmin (match_grad.hip): dense_match_partial_kernel / dense_match_finalize_kernel with an index beside
+// every minimum.  Defined in correlation.hip, next to the kernels; the arguments arrive validated.
+size_t aoc_dense_argmin_workspace_bytes_impl(int64_t m, int64_t n_fg_capacity, int n_obj);
+int aoc_dense_match_argmin_impl(const float *query, int64_t m, int C, const float *pool, const int32_t *fg_rows, const int32_t *n_fg,
+                                int64_t n_fg_capacity, const uint32_t *wrong_bits, const float *obj_bias, int n_obj, float *out, int32_t *arg,
+                                int64_t out_pixel_stride, int64_t out_obj_stride, int transform, void *workspace, aoc_stream_t stream);
+
 // measurement probe of aoc_dense_match_set_probe (thread-local; defined in correlation.hip)
 struct AocDenseProbe { hipEvent_t start, stop; };
 AocDenseProbe aoc_take_dense_probe();

@@ -306,12 +306,16 @@ struct DenseBTile {
 // waves; the NEXT chunk's row ids and rows are fetched into registers while the current chunk is multiplied
 // (loads stay in flight across the barrier, written to LDS after it), so the matrix pipe only idles for the
 // LDS write pass.
-template <int NA, int OMAX, int TMAX, bool EXACT, int NW, bool F16>
-__global__ __launch_bounds__(NW * 64, 2) void dense_match_partial_kernel(const float *__restrict__ query, int64_t m, int C,
+// ARG (aoc_dense_match_argmin): beside every running minimum the position in fg_rows of the column that set it.  The minimum itself is
+// computed by the same instructions in both instantiations, so its bits do not depend on ARG; the position only follows a strict `<`,
+// and a lane meets its columns in ascending position, so ties stay with the lowest one.
+template <int NA, int OMAX, int TMAX, bool EXACT, int NW, bool F16, bool ARG = false>
+__global__ __launch_bounds__(NW * 64, ARG ? 1 : 2) void dense_match_partial_kernel(const float *__restrict__ query, int64_t m, int C,
                                                                           const float *__restrict__ pool, const int32_t *__restrict__ fg_rows,
                                                                           const int32_t *__restrict__ n_fg_ptr, const float *__restrict__ r2_all,
                                                                           const uint32_t *__restrict__ wrong_bits, int n_obj,
-                                                                          float *__restrict__ partial, const int32_t *__restrict__ gate, int obj_base) {
+                                                                          float *__restrict__ partial, const int32_t *__restrict__ gate, int obj_base,
+                                                                          int32_t *__restrict__ partial_arg = nullptr) {
     // objects [obj_base, obj_base + OMAX) of the n_obj: more than 16 objects take a second launch over the same pixels
     if (gate && *gate == 0) return;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -353,6 +357,15 @@ __global__ __launch_bounds__(NW * 64, 2) void dense_match_partial_kernel(const f
         for (int ia = 0; ia < NA; ++ia)
 #pragma unroll
             for (int r = 0; r < 4; ++r) mn[o][ia][r] = INFINITY;
+    int32_t mi[ARG ? OMAX : 1][ARG ? NA : 1][4];      // ARG: position in fg_rows of the column behind mn (-1: none yet)
+    if constexpr (ARG) {
+#pragma unroll
+        for (int o = 0; o < OMAX; ++o)
+#pragma unroll
+            for (int ia = 0; ia < NA; ++ia)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) mi[o][ia][r] = -1;
+    }
 
     auto load_tile = [&](int ti, DenseBTile<NB4> &t) {
         const float *bstream = lds + (size_t)(ti * 16 + j) * RS + g * TP;
@@ -362,7 +375,7 @@ __global__ __launch_bounds__(NW * 64, 2) void dense_match_partial_kernel(const f
         t.r2 = lr2[ti * 16 + j];
         t.wrong = lwrong[ti * 16 + j];
     };
-    auto step = [&](const DenseBTile<NB4> &t) {
+    auto step = [&](const DenseBTile<NB4> &t, int pos) {      // pos: this lane's column as a position in fg_rows (ARG only)
         f32x4 acc[NA];
 #pragma unroll
         for (int ia = 0; ia < NA; ++ia) acc[ia] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -388,7 +401,11 @@ __global__ __launch_bounds__(NW * 64, 2) void dense_match_partial_kernel(const f
                 // AEM:43; float16 mode (AEM:65-66, 801-803): dists, the padded sum and the min are float16 tensors
                 const float d = F16 ? aoc_h(aoc_h(q2r[ia][r] + t.r2) - 2.0f * aoc_h(acc[ia][r])) : (q2r[ia][r] + t.r2) - 2.0f * acc[ia][r];
 #pragma unroll
-                for (int o = 0; o < OMAX; ++o) mn[o][ia][r] = aoc_fmin_raw(mn[o][ia][r], F16 ? aoc_h(d + padv[o]) : d + padv[o]);   // AEM:88
+                for (int o = 0; o < OMAX; ++o) {
+                    const float cand = F16 ? aoc_h(d + padv[o]) : d + padv[o];
+                    if constexpr (ARG) mi[o][ia][r] = cand < mn[o][ia][r] ? pos : mi[o][ia][r];
+                    mn[o][ia][r] = aoc_fmin_raw(mn[o][ia][r], cand);   // AEM:88
+                }
             }
     };
 
@@ -478,9 +495,9 @@ __global__ __launch_bounds__(NW * 64, 2) void dense_match_partial_kernel(const f
         load_tile(0, t0);
         for (int ti = 0; ti < nt; ti += 2) {
             if (ti + 1 < nt) load_tile(ti + 1, t1);
-            step(t0);
+            step(t0, (chunk + ti) * 16 + j);
             if (ti + 2 < nt) load_tile(ti + 2, t0);
-            if (ti + 1 < nt) step(t1);
+            if (ti + 1 < nt) step(t1, (chunk + ti + 1) * 16 + j);
         }
         __syncthreads();                              // every wave is done reading this chunk
         if (more) {
@@ -497,36 +514,61 @@ __global__ __launch_bounds__(NW * 64, 2) void dense_match_partial_kernel(const f
 #pragma unroll
             for (int ia = 0; ia < NA; ++ia) {
                 float v = 0.0f;
+                int32_t vi = -1;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     float mr = aoc_min16(mn[o][ia][r]);
                     if (j == r) v = mr;
+                    if constexpr (ARG) {      // the lowest position among the lanes that hold the minimum (-1 when every candidate was +inf)
+                        int32_t pi = mn[o][ia][r] == mr ? mi[o][ia][r] : INT32_MAX;
+                        pi = min(pi, __shfl_xor(pi, 1));
+                        pi = min(pi, __shfl_xor(pi, 2));
+                        pi = min(pi, __shfl_xor(pi, 4));
+                        pi = min(pi, __shfl_xor(pi, 8));
+                        if (j == r) vi = pi;
+                    }
                 }
                 const int64_t row = wave_row0 + ia * 16 + g * 4 + j;
                 if (j < 4 && row < m) partial[((int64_t)blockIdx.y * m + row) * n_obj + obj_base + o] = v;
+                if constexpr (ARG) {
+                    if (j < 4 && row < m) partial_arg[((int64_t)blockIdx.y * m + row) * n_obj + obj_base + o] = vi;
+                }
             }
         }
     }
 }
 
+// ARG: also arg[row, o] = the pool row behind the minimum; splits hold ascending position ranges and fg_rows ascends, so the strict `<`
+// over ascending s keeps the lowest pool row on ties.  -1 when the winner is a padded distance (>= AOC_PAD_DISTANCE / 2) or nothing is kept.
+template <bool ARG = false>
 __global__ __launch_bounds__(256) void dense_match_finalize_kernel(const float *__restrict__ partial, int n_split, int64_t m, int n_obj,
                                                                     const int32_t *__restrict__ n_fg_ptr, const float *__restrict__ obj_bias,
                                                                     float *__restrict__ out, int64_t pstride, int64_t ostride, int transform,
-                                                                    const int32_t *__restrict__ gate) {
+                                                                    const int32_t *__restrict__ gate, const int32_t *__restrict__ partial_arg = nullptr,
+                                                                    const int32_t *__restrict__ fg_rows = nullptr, int32_t *__restrict__ arg = nullptr) {
     if (gate && *gate == 0) return;
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= m * n_obj) return;
     const int64_t row = idx / n_obj;
     const int o = (int)(idx - row * n_obj);
     float v;
+    int32_t a = -1;
     if (*n_fg_ptr == 0) {
         v = transform ? 1.0f : INFINITY;   // AEM:796-797: nothing labelled -> ones
     } else {
         v = INFINITY;
-        for (int s = 0; s < n_split; ++s) v = fminf(v, partial[((int64_t)s * m + row) * n_obj + o]);
+        for (int s = 0; s < n_split; ++s) {
+            const float pv = partial[((int64_t)s * m + row) * n_obj + o];
+            if constexpr (ARG) {
+                if (pv < v) a = partial_arg[((int64_t)s * m + row) * n_obj + o];
+            }
+            v = fminf(v, pv);
+        }
+        if constexpr (ARG) a = (a >= 0 && v < 0.5f * AOC_PAD_DISTANCE) ? fg_rows[a] : -1;
         if (transform) v = aoc_proto_transform(v, obj_bias ? obj_bias[o] : 0.0f);
     }
     out[row * pstride + o * ostride] = v;
+    if constexpr (ARG) arg[row * pstride + o * ostride] = a;
 }
 
 constexpr int DM_NW = 8;   // waves per block
@@ -732,8 +774,47 @@ int aoc_dense_match_min_gated(const float *query, int64_t m, int C, const float 
     }
     if (probe.stop) (void)hipEventRecord(probe.stop, st);
     const int64_t total = m * n_obj;
-    hipLaunchKernelGGL(dense_match_finalize_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, partial, ns, m, n_obj, n_fg,
-                       obj_bias, out, out_pixel_stride, out_obj_stride, transform, gate);
+    hipLaunchKernelGGL(dense_match_finalize_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, partial, ns, m, n_obj, n_fg,
+                       obj_bias, out, out_pixel_stride, out_obj_stride, transform, gate, nullptr, nullptr, nullptr);
+    AOC_RETURN_IF_LAUNCH_FAILED();
+    return AOC_OK;
+}
+
+// aoc_dense_match_argmin (match_grad.hip validates): the launches of aoc_dense_match_min_gated's fp32 path with ARG = true, with an
+// n-split of its own (dense_nsplit(m, 1): one A tile per wave, where the plain entry has two for up to four objects) and the same
+// ascending candidate order per lane; a minimum is exact, so its bits depend neither on the n-split nor on how the objects are sliced.  Objects
+// go four at a time over one A tile per wave, so that the positions fit the registers beside the minima (the kernel is at its register
+// budget without them).
+size_t aoc_dense_argmin_workspace_bytes_impl(int64_t m, int64_t n_fg_capacity, int n_obj) {
+    const int ns = dense_nsplit(m, 1);
+    return aoc_align_up((size_t)n_fg_capacity * sizeof(float) + 16, 256) + 2 * aoc_align_up((size_t)ns * m * n_obj * sizeof(float), 256);
+}
+
+int aoc_dense_match_argmin_impl(const float *query, int64_t m, int C, const float *pool, const int32_t *fg_rows, const int32_t *n_fg,
+                                int64_t n_fg_capacity, const uint32_t *wrong_bits, const float *obj_bias, int n_obj, float *out, int32_t *arg,
+                                int64_t out_pixel_stride, int64_t out_obj_stride, int transform, void *workspace, aoc_stream_t stream) {
+    hipStream_t st = aoc_hip_stream(stream);
+    const size_t r2_bytes = aoc_align_up((size_t)n_fg_capacity * sizeof(float) + 16, 256);
+    const int na = 1;
+    const int ns = dense_nsplit(m, na);
+    const size_t part_bytes = aoc_align_up((size_t)ns * m * n_obj * sizeof(float), 256);
+    float *r2 = static_cast<float *>(workspace);
+    float *partial = reinterpret_cast<float *>(static_cast<char *>(workspace) + r2_bytes);
+    int32_t *partial_arg = reinterpret_cast<int32_t *>(static_cast<char *>(workspace) + r2_bytes + part_bytes);
+    const int row_blocks = (int)((m + 16 * DM_NW * na - 1) / (16 * DM_NW * na));
+    const int RS = aoc_tile_row_stride(C);
+    const size_t lds = (size_t)DM_NB * 16 * RS * sizeof(float) + DM_NB * 16 * (sizeof(float) + sizeof(uint32_t) + 2 * sizeof(int32_t));
+    const int32_t *gate = nullptr;
+    hipLaunchKernelGGL(gather_sqnorm_kernel<false>, dim3((unsigned)((n_fg_capacity + 255) / 256)), dim3(256), 0, st, pool, C, fg_rows, n_fg, r2, gate);
+    const dim3 grid(row_blocks, ns);
+    for (int obj_base = 0; obj_base < n_obj; obj_base += 4) {
+#define AOC_DMA(NA, OM, TM, EX) hipLaunchKernelGGL((dense_match_partial_kernel<NA, OM, TM, EX, DM_NW, false, true>), grid, dim3(DM_NW * 64), lds, st, query, m, C, pool, fg_rows, n_fg, r2, wrong_bits, n_obj, partial, gate, obj_base, partial_arg)
+        if (C == 100) AOC_DMA(1, 4, 25, true); else AOC_DMA(1, 4, 32, false);
+#undef AOC_DMA
+    }
+    const int64_t total = m * n_obj;
+    hipLaunchKernelGGL(dense_match_finalize_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, partial, ns, m, n_obj, n_fg,
+                       obj_bias, out, out_pixel_stride, out_obj_stride, transform, gate, partial_arg, fg_rows, arg);
     AOC_RETURN_IF_LAUNCH_FAILED();
     return AOC_OK;
 }

@@ -23,15 +23,21 @@ def _need_gpu(*tensors):
                                    f"got a tensor on {t.device}")
 
 
+# mirrors whose training twin has a backward in matching_train (keyed by the name the guard is called with)
+_TRAINABLE = {"global_matching_for_eval": "global_matching", "global_matching_for_eval_proxy": "global_matching_proxy"}
+
+
 def inference_only(what, *tensors):
-    """The HIP kernels have no backward: every mirror returns tensors WITHOUT an autograd graph.  Dropping the reference's
+    """The HIP kernels of the mirrors have no backward: every mirror returns tensors WITHOUT an autograd graph.  Dropping the reference's
     training-time names (IA_gate, conditioning_block, GCT, global_matching, ...) into a training run would therefore train
-    nothing, silently.  Raise instead when autograd is recording and an input or parameter wants a gradient."""
+    nothing, silently.  Raise instead when autograd is recording and an input or parameter wants a gradient.  The two functions that
+    do have a backward, global_matching and global_matching_proxy, live in aoc_amd.matching_train; the error text says so for them."""
     if torch.is_grad_enabled():
         for t in tensors:
             if torch.is_tensor(t) and t.requires_grad:
+                hint = ("; aoc_amd.matching_train." + _TRAINABLE[what] + " is the differentiable form") if what in _TRAINABLE else ""
                 raise _lib.AocHipError(f"aoc_amd.{what} is inference-only (no autograd graph is built): call it under torch.no_grad() "
-                                       "or detach its inputs; training must use the reference's PyTorch modules")
+                                       "or detach its inputs; training must use the reference's PyTorch modules" + hint)
 
 
 def _p(t):
@@ -350,6 +356,76 @@ def dense_match_min(query_flat, pool, prep, obj_bias, out, out_pixel_stride, out
                   _p(obj_bias), n_obj, _p(out), int(out_pixel_stride), int(out_obj_stride), int(bool(transform)),
                   _p(ws), ws.numel(), _stream()), "aoc_dense_match_min_f16" if float16 else "aoc_dense_match_min")
     return out
+
+
+def dense_match_argmin(query_flat, pool, prep, obj_bias, out, arg, out_pixel_stride, out_obj_stride, transform=True):
+    """aoc_dense_match_argmin: dense_match_min's values (bit for bit) and, in ``arg`` (int32, addressed like ``out``), the pool row of every
+    minimum; -1 where the winner is a padded distance or nothing is labelled."""
+    query_flat = _f32c(query_flat)
+    pool = _f32c(pool)
+    _need_gpu(query_flat, pool, out, arg)
+    assert arg.dtype == torch.int32
+    m, C = query_flat.shape
+    n_obj = prep.n_obj
+    L = _lib.lib()
+    ws = _ws(L.aoc_dense_match_argmin_workspace_bytes(m, prep.n, n_obj), pool.device)
+    if obj_bias is not None:
+        obj_bias = _f32c(obj_bias)
+    n_fg = prep.counts[n_obj:n_obj + 1]
+    _lib.check(L.aoc_dense_match_argmin(_p(query_flat), m, C, _p(pool), _p(prep.fg_rows), _p(n_fg), prep.n, _p(prep.wrong_bits),
+                                        _p(obj_bias), n_obj, _p(out), _p(arg), int(out_pixel_stride), int(out_obj_stride), int(bool(transform)),
+                                        _p(ws), ws.numel(), _stream()), "aoc_dense_match_argmin")
+    return out, arg
+
+
+def dense_match_backward(grad_out, T, arg, pixel_stride, obj_stride, query_flat, pool, n_obj, want_query=True, want_pool=True, want_bias=True,
+                         grad_query=None, grad_pool=None, grad_bias=None):
+    """aoc_dense_match_grad.  grad_out, T and arg are addressed as [i * pixel_stride + o * obj_stride] from their data pointers.
+    -> (grad_query [m, C], grad_pool [n, C], grad_bias [n_obj]); None for an output that is not wanted (nothing is written for it).  The
+    keyword buffers, when given, are written in place."""
+    query_flat = _f32c(query_flat)
+    pool = _f32c(pool)
+    _need_gpu(grad_out, T, arg, query_flat, pool, grad_query, grad_pool, grad_bias)
+    assert grad_out.dtype == torch.float32 and T.dtype == torch.float32 and arg.dtype == torch.int32
+    m, C = query_flat.shape
+    n = pool.shape[0]
+    dev = pool.device
+    if want_query and grad_query is None:
+        grad_query = torch.empty(m, C, dtype=torch.float32, device=dev)
+    if want_pool and grad_pool is None:
+        grad_pool = torch.empty(n, C, dtype=torch.float32, device=dev)
+    if want_bias and grad_bias is None:
+        grad_bias = torch.empty(n_obj, dtype=torch.float32, device=dev)
+    gq, gp, gb = (grad_query if want_query else None), (grad_pool if want_pool else None), (grad_bias if want_bias else None)
+    L = _lib.lib()
+    ws = _ws(L.aoc_dense_match_grad_workspace_bytes(m, n, C, n_obj), dev)
+    _lib.check(L.aoc_dense_match_grad(_p(grad_out), _p(T), _p(arg), int(pixel_stride), int(obj_stride), _p(query_flat), m, C, _p(pool), n, n_obj,
+                                      _p(gq), _p(gp), _p(gb), _p(ws), ws.numel(), _stream()), "aoc_dense_match_grad")
+    return gq, gp, gb
+
+
+def proxy_match_backward(grad_out, T, pixel_stride, obj_stride, query_flat, proxies, want_query=True, want_proxies=True, want_bias=True,
+                         grad_query=None, grad_proxies=None, grad_bias=None):
+    """aoc_proxy_match_grad (k = 1 proxies [n_obj, C]).  -> (grad_query, grad_proxies, grad_bias), None where not wanted."""
+    query_flat = _f32c(query_flat)
+    proxies = _f32c(proxies)
+    _need_gpu(grad_out, T, query_flat, proxies, grad_query, grad_proxies, grad_bias)
+    assert grad_out.dtype == torch.float32 and T.dtype == torch.float32
+    m, C = query_flat.shape
+    n_obj = proxies.shape[0]
+    dev = query_flat.device
+    if want_query and grad_query is None:
+        grad_query = torch.empty(m, C, dtype=torch.float32, device=dev)
+    if want_proxies and grad_proxies is None:
+        grad_proxies = torch.empty(n_obj, C, dtype=torch.float32, device=dev)
+    if want_bias and grad_bias is None:
+        grad_bias = torch.empty(n_obj, dtype=torch.float32, device=dev)
+    gq, gp, gb = (grad_query if want_query else None), (grad_proxies if want_proxies else None), (grad_bias if want_bias else None)
+    L = _lib.lib()
+    ws = _ws(L.aoc_proxy_match_grad_workspace_bytes(m, C, n_obj), dev)
+    _lib.check(L.aoc_proxy_match_grad(_p(grad_out), _p(T), int(pixel_stride), int(obj_stride), _p(query_flat), m, C, _p(proxies), n_obj,
+                                      _p(gq), _p(gp), _p(gb), _p(ws), ws.numel(), _stream()), "aoc_proxy_match_grad")
+    return gq, gp, gb
 
 
 class SplitRows:
