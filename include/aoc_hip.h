@@ -123,6 +123,8 @@ int aoc_kmeans_replicate_levels(const int32_t *rows, const int32_t *seg_offsets,
  *  centroids    [n_seg, kmax, C] out   final code book
  *  labels       [rows_capacity]  out   segment-local cluster id of every packed row (last assignment)
  *  cluster_counts [n_seg, kmax]  out   members per cluster in the last update
+ * Slots j >= seg_k[s] (every slot of a skipped segment) come back as zero centroids and zero counts; the labels of a skipped
+ * segment are not written.  An init_rows entry outside its segment is clamped into it.
  */
 size_t aoc_kmeans_workspace_bytes(int64_t rows_capacity, int n_seg, int kmax, int C);
 /* Same, with the number of rows of `pool` stated (pool_rows > 0): enables the pipelined ordered

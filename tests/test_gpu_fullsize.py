@@ -235,8 +235,11 @@ def test_kmeans_bit_exact_with_the_single_pass_tail():
     if not os.path.exists(aoc_amd._lib.DEV_SO):
         pytest.skip("development build not present (make DEV=1)")
     env = dict(os.environ, AOC_KM_FUSED="1", AOC_LIB_VARIANT="dev")
+    # test_gpu_kmeans_paths.py: its k-means and proxy cases (adversarial tails: exact ties, crossings, moving membership), not its label lists
     r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", os.path.join(here, "test_gpu_fullsize.py"), os.path.join(here, "test_gpu_parity.py"),
-                        "-k", "kmeans and not single_pass and not persistent"], env=env, capture_output=True, text=True, timeout=900)
+                        os.path.join(here, "test_gpu_kmeans_paths.py"),
+                        "-k", "kmeans and not single_pass and not persistent and not label_prep and not replicate and not kmeans_plan"],
+                       env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
 
 
