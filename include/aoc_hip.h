@@ -15,6 +15,19 @@
  *  - work is enqueued on `stream` (a hipStream_t passed as void*) and NOT synchronised;
  *  - return value: 0 = enqueued, < 0 = aoc_status error (nothing enqueued); never throws;
  *  - fp32 data, row-major; "rows" are pixels of stride-4 feature maps; C = embedding width.
+ *
+ * Workspaces
+ *  A `workspace` argument may hold ANYTHING on entry -- another call's leftovers, another shape's, uninitialised memory -- unless the
+ *  entry says otherwise: every entry initialises what it reads, and its results do not depend on what the bytes held
+ *  (tests/test_gpu_carried_state.py runs each one in a zeroed workspace, in one of all-ones words and in one a larger case has just
+ *  used, and wants the same bits).  A workspace is used by one stream at a time.  The entries that say otherwise:
+ *   - aoc_proxy_corr_min_batched, aoc_proxy_corr_min_records, aoc_proxy_corr_min_records_cached: the take-over flag word is zeroed by
+ *     the caller once after allocation and never reset; the cached form also keeps its pass tables there, described by *tables_key
+ *     (0 = nothing cached: a workspace that is new, or was used for anything else, goes with a key of 0);
+ *   - aoc_mask_jf_accumulate with workspace_is_clean != 0: the counters are zero on entry (the call leaves them zeroed);
+ *   - aoc_dense_match_min_split_cached with reuse_plan != 0: the workspace holds what the last reuse_plan = 0 call for the same pool
+ *     state and the same m left there, and nothing else has written to it since;
+ *   - aoc_frame_enqueue: the workspace's content is described by the caller's aoc_seq_state; a zeroed state record goes with any content.
  */
 #ifndef AOC_HIP_H
 #define AOC_HIP_H
@@ -392,7 +405,19 @@ int aoc_dense_match_min_split(const float *query, const void *query_rec, const f
 /* The same call for a caller that keeps `workspace` across the frames that see ONE pool state (same pool rows, labels and records):
  * reuse_plan = 0 builds the plan (object-pure tile lists, norm maxima, one-hot check: a function of the pool alone) and leaves it in the
  * workspace; reuse_plan = 1 skips the plan kernel and both memsets (the finalize kernel of every call leaves the per-pixel bounds zeroed)
- * and only refreshes the gate from the sticky overflow flag.  Results are identical to aoc_dense_match_min_split. */
+ * and only refreshes the gate from the sticky overflow flag.  Results are always within the bound of aoc_dense_match_min_split, and
+ * identical to it bit for bit while the gate kept in the workspace agrees with the one that call would compute (the one case where it
+ * does not: the first item below).
+ * What a reusing call may assume of the call before it in the same workspace (tests/test_gpu_carried_state.py):
+ *  - after a take-over frame (the overflow flag was raised, or the plan's one-hot check failed): every split kernel, the finalize
+ *    kernel included, returned at the gate, so the per-pixel bounds are still the zeros the frame found.  The gate itself stays set
+ *    in the workspace even if the caller clears the flag: every later reusing call is answered by the exact-fp32 kernels (correct,
+ *    bit-identical to aoc_dense_match_min) until a reuse_plan = 0 call, made with the flag cleared, builds the plan again;
+ *  - after a frame with n_fg = 0 (counts all zero): the plan has no tile, nothing was written to the bounds, the output was the
+ *    constant (1.0 transformed, +inf raw); reusing calls give the same while the pool state stands;
+ *  - an object with counts[o] = 0 has a bounds column that no kernel reads or writes: it keeps the zeros of the build;
+ *  - m, n, n_obj and C are those of the build (they place the plan inside the workspace); a new pool state, of any size that fits,
+ *    starts with reuse_plan = 0 in the same bytes. */
 int aoc_dense_match_min_split_cached(const float *query, const void *query_rec, const float *query_sqnorm, int query_rec_tiled,
                               int64_t m, int C, const float *pool, const void *pool_rec,
                               const int32_t *overflow_flag, int64_t n,
