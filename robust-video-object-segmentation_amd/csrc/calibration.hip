@@ -348,57 +348,6 @@ __device__ __forceinline__ float film_gain_wg256(const float *__restrict__ h, co
     return 1.0f + tanhf((wsum[0] + wsum[1] + wsum[2] + wsum[3]) + (bias ? bias[c] : 0.0f));
 }
 
-#ifdef AOC_DEV
-// FiLM gate in one launch: every block first computes its plane's gain 1 + tanh(head[o,:].W[c,:] + b[c]) (a D-long
-// dot product, block-reduced), then streams its slice of the plane.  Saves the separate gain launch + round trip.
-__global__ __launch_bounds__(256) void film_scale_kernel(const float *__restrict__ x, const float *__restrict__ head, const float *__restrict__ weight,
-                                                          const float *__restrict__ bias, int D, int channels, int64_t hw, float *__restrict__ y, int nt) {
-    __shared__ float wsum[4];
-    const int64_t plane = blockIdx.y;
-    const int o = (int)(plane / channels), c = (int)(plane - (int64_t)o * channels);
-    const float g = film_gain_wg256(head + (size_t)o * D, weight + (size_t)c * D, bias, c, D, wsum);
-    const float *xp = x + plane * hw;
-    float *yp = y + plane * hw;
-    const uintptr_t addr = reinterpret_cast<uintptr_t>(xp);
-    int64_t headn = ((16 - (addr & 15)) & 15) / 4;
-    if (headn > hw) headn = hw;
-    const bool same_align = ((reinterpret_cast<uintptr_t>(yp) & 15) == (addr & 15));
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
-    if (same_align) {
-        if (tid < headn) yp[tid] = g * xp[tid];
-        const int64_t body4 = (hw - headn) / 4;
-        const float4 *x4 = reinterpret_cast<const float4 *>(xp + headn);
-        float4 *y4 = reinterpret_cast<float4 *>(yp + headn);
-        for (int64_t i0 = tid; i0 < body4; i0 += 4 * nthreads) {     // four strides per trip, all loads in flight before the first store
-            float4 v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int64_t i = i0 + u * nthreads;
-                v[u] = x4[i < body4 ? i : body4 - 1];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int64_t i = i0 + u * nthreads;
-                if (i < body4) {
-                    v[u].x *= g; v[u].y *= g; v[u].z *= g; v[u].w *= g;
-                    if (nt) {
-                        typedef float f32x4_t __attribute__((ext_vector_type(4)));
-                        __builtin_nontemporal_store(f32x4_t{v[u].x, v[u].y, v[u].z, v[u].w}, reinterpret_cast<f32x4_t *>(y4 + i));
-                    } else {
-                        y4[i] = v[u];
-                    }
-                }
-            }
-        }
-        const int64_t tail0 = headn + body4 * 4;
-        if (tid < hw - tail0) yp[tail0 + tid] = g * xp[tail0 + tid];
-    } else {
-        for (int64_t i = tid; i < hw; i += nthreads) yp[i] = g * xp[i];
-    }
-}
-#endif  // AOC_DEV
-
 // FiLM gate in one launch: y[o,c,:] = (1 + tanh(head[o,:].W[c,:] + b[c])) x[o,c,:]  (ATT:12-17, CLB:81-84), the gain computed by every workgroup
 // of the plane (a D-long dot product, block-reduced) -- no separate gain launch.  The workgroup's whole slice of the plane is requested BEFORE
 // the dot product: a workgroup lives for one memory round
@@ -1505,17 +1454,7 @@ int aoc_film_scale(const float *x, const float *head, const float *weight, const
     // the full-resolution maps (tools/bench_gates.py).  Loads and stores are nontemporal: the activation is read once and the gated copy is a
     // pure stream-out -- every dirty line it would leave in the XCDs' L2s is written back at the next kernel boundary of ANY stream, and the
     // k-means chain on the side stream has ~100 of them per frame (bench: +2 % frames/s when the stores went nontemporal in round 3).
-    static const int ahead = AOC_DEV_ENV_INT("AOC_FILM_AHEAD", -1);
-    const int U = ahead == 4 || ahead == 8 ? ahead : (hw / 4 <= 2048 ? 8 : 4);
-#ifdef AOC_DEV
-    if (ahead == 0) {                                           // the kernel of rounds 2-4 (dot product first, then the stream)
-        static const int nt = AOC_DEV_ENV_INT("AOC_FILM_NT", 1);
-        const int bx = (int)std::min<int64_t>(8, std::max<int64_t>(1, (hw / 4 + 255) / 256));
-        hipLaunchKernelGGL(film_scale_kernel, dim3(bx, (unsigned)planes), dim3(256), 0, aoc_hip_stream(stream), x, head, weight, bias, head_dim, channels, hw, y, nt);
-        AOC_RETURN_IF_LAUNCH_FAILED();
-        return AOC_OK;
-    }
-#endif
+    const int U = hw / 4 <= 2048 ? 8 : 4;
     const int64_t per_wg = 256 * (int64_t)U;
     const unsigned gx = (unsigned)std::max<int64_t>(1, (hw / 4 + per_wg - 1) / per_wg);
     const int chunk = (int)std::max<int64_t>(1, (hw / 4 + gx - 1) / gx);
@@ -1593,12 +1532,11 @@ int aoc_cond_gate_pool_ex(const float *z, int N, int C, int64_t hw, const float 
     hipLaunchKernelGGL(cond_scores_part_kernel, dim3((unsigned)w.n_part, (unsigned)w.n_chunks, N), dim3(256), 0, st, z, C, hw, phi_w, w.part_scores, w.partial,
                        w.hist);
     hipLaunchKernelGGL(cond_scores_reduce_kernel, pgrid, dim3(CS_PIX), 0, st, w.part_scores, w.n_chunks, hw, phi_b, sc, w.hist);
-    static const int tail = AOC_DEV_ENV_INT("AOC_COND_TAIL", 1);
-    if (tail && hw <= 8 * 1024)
+    if (hw <= 8 * 1024)
         hipLaunchKernelGGL(cond_select_tail_kernel<8>, dim3(N), dim3(1024), 0, st, sc, hw, k_rank, w.hist, w.sel);
-    else if (tail && hw <= 32 * 1024)
+    else if (hw <= 32 * 1024)
         hipLaunchKernelGGL(cond_select_tail_kernel<32>, dim3(N), dim3(1024), 0, st, sc, hw, k_rank, w.hist, w.sel);
-    else if (tail && hw <= 64 * 1024)
+    else if (hw <= 64 * 1024)
         hipLaunchKernelGGL(cond_select_tail_kernel<64>, dim3(N), dim3(1024), 0, st, sc, hw, k_rank, w.hist, w.sel);
     else
         for (int pass = 1; pass <= 3; ++pass)                     // larger maps: one launch per digit, spread over the GPU

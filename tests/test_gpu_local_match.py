@@ -6,9 +6,7 @@ _check_bound once per slip of local_slips(case): the same reference with one del
 test_local_match_host.py proves without a GPU that the reference is the oracle's local_matching, that float32 restatements of both kernels
 lie inside the bound and that every slip leaves it, at every case of this file.
 
-C = 100 / 128 take local_window_reg_kernel, every other C local_window_kernel<32> (the LDS-image kernel).  local_window_row_kernel is not
-tested: in the release library C = 100 / 128 always take the register kernel, so the row kernel can only be reached through a developer
-switch of the development build, and none is added for it."""
+C = 100 / 128 take local_window_reg_kernel, every other C local_window_kernel<32> (the LDS-image kernel): the two kernels the file has."""
 import ctypes
 
 import numpy as np

@@ -1,14 +1,13 @@
 #!/usr/bin/env python3
 """Stand-alone timing of local (windowed) matching on an idle GPU at the half-resolution map of a config (AEM:938-941):
 
-    python tools/bench_local.py [--config cfg2] [--kernels reg,row,block]
+    python tools/bench_local.py [--config cfg2]
 
-One JSON object per kernel variant (each in a child process: the variant is a library-level developer switch, AOC_LOCAL_KERNEL, read
-once): median launch time (HIP events), flops 2 m (2R+1)^2 C and the max |difference| of the outputs against the first variant."""
+One JSON object: median launch time (HIP events) of the kernel the library takes for the config's channel count (C = 100 / 128:
+local_window_reg_kernel) and flops 2 m (2R+1)^2 C."""
 import argparse
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -30,11 +29,14 @@ def timed(fn, reps=40):
     return float(np.median([ev[i].elapsed_time(ev[i + 1]) for i in range(reps)]))
 
 
-def child(config, dump):
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="cfg2")
+    args = ap.parse_args()
     import aoc_amd  # noqa: F401
     from aoc_amd import ops
     from aoc_amd import synthetic as syn
-    cfg = syn.CONFIGS[config]
+    cfg = syn.CONFIGS[args.config]
     clip = syn.make_clip(cfg, seed=3, frames=2)
     dev = torch.device("cuda")
     O = cfg.n_obj
@@ -48,34 +50,9 @@ def child(config, dump):
     bits2 = ops.resize_nearest_bits(bits, cfg.h, cfg.w, H2, W2)
     radii = [2, 4, 6, 8, 10, 12]
     bias = torch.zeros(O, device=dev)
-    out = ops.local_window_match(q2, p2, bits2, radii, bias, O, True)
     ms = timed(lambda: ops.local_window_match(q2, p2, bits2, radii, bias, O, True))
-    np.save(dump, out.cpu().numpy())
     flops = 2.0 * H2 * W2 * 25 * 25 * cfg.c
-    print(json.dumps(dict(kernel=os.environ.get("AOC_LOCAL_KERNEL", "reg"), map=[H2, W2], ms=round(ms, 4), tflops=round(flops / ms * 1e-9, 2))), flush=True)
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--config", default="cfg2")
-    ap.add_argument("--kernels", default="reg,row,block")
-    ap.add_argument("--child", default="")
-    args = ap.parse_args()
-    if args.child:
-        child(args.config, args.child)
-        return
-    ref = None
-    for k in args.kernels.split(","):
-        env = dict(os.environ)
-        env["AOC_LOCAL_KERNEL"] = k
-        env["AOC_LIB_VARIANT"] = "dev"            # library-level switches only exist in the development build
-        dump = "/tmp/bench_local_%s.npy" % k
-        subprocess.run([sys.executable, os.path.abspath(__file__), "--config", args.config, "--child", dump], env=env, check=True)
-        o = np.load(dump)
-        if ref is None:
-            ref = o
-        else:
-            print(json.dumps(dict(kernel=k, max_abs_diff_vs_first=float(np.abs(o - ref).max()))), flush=True)
+    print(json.dumps(dict(map=[H2, W2], ms=round(ms, 4), tflops=round(flops / ms * 1e-9, 2))), flush=True)
 
 
 if __name__ == "__main__":
