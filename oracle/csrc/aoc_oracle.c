@@ -69,6 +69,24 @@ void aoc_oracle_vq(const float *obs, const float *code, int n, int k, int d,
     free(code_sqr);
 }
 
+/* The three float32 operands of every distance of aoc_oracle_vq, each rounded exactly as there: dot[i,j] the k-ordered fmaf chain
+ * from 0, obs_sqr[i] and code_sqr[j] the sequential multiply-then-add norms.  tests/test_kmeans_host.py combines them in numpy
+ * float32 (one IEEE operation per step) to show which rows tell the order (-2 dot + |x|^2) + |c|^2 apart from other ones. */
+void aoc_oracle_vq_parts(const float *obs, const float *code, int n, int k, int d,
+                         float *dot, float *obs_sqr, float *code_sqr) {
+    for (int j = 0; j < k; ++j) code_sqr[j] = sq_norm_seq(code + (size_t)j * d, d);
+    for (int i = 0; i < n; ++i) {
+        const float *x = obs + (size_t)i * d;
+        obs_sqr[i] = sq_norm_seq(x, d);
+        for (int j = 0; j < k; ++j) {
+            const float *c = code + (size_t)j * d;
+            float acc = 0.0f;
+            for (int t = 0; t < d; ++t) acc = fmaf(x[t], c[t], acc);
+            dot[(size_t)i * k + j] = acc;
+        }
+    }
+}
+
 /* scipy _vq.update_cluster_means + the empty-cluster rule of vq.py:820-823.
  * code is updated in place; counts[j] receives the member count. */
 void aoc_oracle_update_means(const float *obs, const int32_t *labels, int n, int k, int d,

@@ -31,6 +31,8 @@ def lib():
         vp, ci = ctypes.c_void_p, ctypes.c_int
         L.aoc_oracle_vq.argtypes = [vp, vp, ci, ci, ci, vp, vp]
         L.aoc_oracle_vq.restype = None
+        L.aoc_oracle_vq_parts.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp]
+        L.aoc_oracle_vq_parts.restype = None
         L.aoc_oracle_update_means.argtypes = [vp, vp, ci, ci, ci, vp, vp]
         L.aoc_oracle_update_means.restype = None
         L.aoc_oracle_kmeans2.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp]
@@ -55,6 +57,29 @@ def vq(obs, code):
     low = np.empty(n, np.float32)
     lib().aoc_oracle_vq(_p(obs), _p(code), n, k, d, _p(labels), _p(low))
     return labels, low
+
+
+def vq_parts(obs, code):
+    """The float32 operands of ``vq``'s distances: (dot [n, k] fmaf chains, obs_sqr [n], code_sqr [k]), so that
+    ``(np.float32(-2) * dot + obs_sqr[:, None]) + code_sqr`` evaluated in numpy float32 is the distance ``vq`` compares."""
+    obs = np.ascontiguousarray(obs, np.float32)
+    code = np.ascontiguousarray(code, np.float32)
+    n, d = obs.shape
+    k = code.shape[0]
+    dot, xs, cs = np.empty((n, k), np.float32), np.empty(n, np.float32), np.empty(k, np.float32)
+    lib().aoc_oracle_vq_parts(_p(obs), _p(code), n, k, d, _p(dot), _p(xs), _p(cs))
+    return dot, xs, cs
+
+
+def update_means(obs, labels, code):
+    """scipy ``_vq.update_cluster_means`` with the empty-cluster rule -> (new code book, counts); ``code`` is not modified."""
+    obs = np.ascontiguousarray(obs, np.float32)
+    labels = np.ascontiguousarray(labels, np.int32)
+    code = np.array(code, np.float32, order="C", copy=True)
+    n, d = obs.shape
+    counts = np.empty(code.shape[0], np.int32)
+    lib().aoc_oracle_update_means(_p(obs), _p(labels), n, code.shape[0], d, _p(code), _p(counts))
+    return code, counts
 
 
 def kmeans2_matrix(obs, init, iters=20, trace=False):

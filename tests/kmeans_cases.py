@@ -12,6 +12,8 @@ References:
   proxy set 1      ordered mean of pool[fg_rows[p]] over the segment-local p with labels[beg + p] == j (AEM:280, bug-compatible)
   label prep       torch on the CPU: labels > 0.9, labels < 0.1, labels.sum(1) > 0.9; lists by np.nonzero
   plan / replicate the few lines of numpy include/aoc_hip.h describes
+  assignment       the oracle's own distance operands (oracle.kmeans.vq_parts) combined in numpy float32; lane_argmin restates the matrix-pipe
+                   argmin from the slot layout, rep_plan the host's choice of kernel, replica groups and grid
 """
 import functools
 
@@ -37,7 +39,8 @@ def clamp_init(init, length):
 
 class KmCase:
     """One aoc_kmeans_segmented_ex call.  pool [P, C] float32; rows int32 packed row ids; offs int32 [S + 1]; seg_k int32 [S];
-    init int32 [S, kmax] segment-local; `claims`: what the sum-walk classifier must find (host test)."""
+    init int32 [S, kmax] segment-local; `claims`: what the sum-walk classifier must find (host test).  n_rep > 1: the lists are already
+    n_rep replicas of S / n_rep base segments (replicate_reference / replicate_levels_reference), for aoc_kmeans_segmented_rep."""
 
     def __init__(self, name, make, claims=()):
         self.name, self._make, self.claims = name, make, tuple(claims)
@@ -59,6 +62,7 @@ class KmCase:
         d.setdefault("iters", 20)
         d["kmax"] = int(d["init"].shape[1])
         d["C"] = int(d["pool"].shape[1])
+        d["n_rep"] = int(d.get("n_rep", 1))
         for a in ("pool", "rows", "offs", "seg_k", "init"):
             d[a].setflags(write=False)
         return d
@@ -265,7 +269,224 @@ def _init_out_of_range():
 ASSIGN_CASES = [KmCase(f"segments_{s}", _many_segments(s)) for s in (128, 129, 180)]
 ASSIGN_CASES += [KmCase("duplicates_K64", _duplicates_k64), KmCase("init_rows_out_of_range", _init_out_of_range)]
 
-KMEANS_CASES = TAIL_CASES + [MOVING_CASE] + WIDTH_CASES + MFMA_CASES + GENERIC_CASES + STITCH_CASES + ASSIGN_CASES
+
+
+# 6. assignment ties.  Both matrix-pipe kernels keep cluster kt * 16 + g * 4 + r in register r of lane group g (tile kt): a lane scans
+# its clusters with a strict <, then the four lane groups merge by two xor exchanges (16, then 32) with "lower distance, then lower index".
+def slot_lane(slot):
+    """(tile kt, lane group g, register r) of a cluster slot."""
+    return slot >> 4, (slot >> 2) & 3, slot & 3
+
+
+# K = 16: the same lane; xor-16 partners; xor-32 partners; two two-step merges.  K = 64: the lower index in the HIGHER lane group through a later
+# tile, for every pair of lane groups -- (1, 0), (2, 0), (3, 0), (3, 1), (3, 0) again across tiles 1 | 2, and (2, 1), (3, 2) -- next to two pairs
+# in index order across tiles 0 | 2 and 1 | 3
+TIE_PAIRS = {16: ((1, 3), (2, 7), (2, 11), (6, 9), (7, 13)),
+             64: ((5, 18), (9, 16), (13, 17), (14, 22), (6, 40), (23, 63), (31, 32), (9, 20), (13, 24))}
+TIE_COPIES = 24
+
+
+def _seg_offsets(lens):
+    return np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+
+
+def _tie_pairs(k, pairs, iters, seed, n_rep=1):
+    """Segments of 200 .. 400 rows; in each, TIE_COPIES rows hold one value that is far from every other row and has so few bits that the mean
+    of its copies is the value itself (the _duplicates_k64 recipe).  Two of the copies are the initial code words of the slot pair
+    pairs[(s + f) % len(pairs)] of segment s in replica f; no other slot starts on a copy.  `pairs` in the result: the pair per segment."""
+    def make():
+        rng = np.random.RandomState(seed)
+        n_seg = 2 * len(pairs) if n_rep == 1 else len(pairs)
+        lens = rng.randint(200, 401, n_seg)
+        offs = _seg_offsets(lens)
+        pool = relu_gauss(rng, int(offs[-1]), 100)
+        init = np.zeros((n_rep * n_seg, k), np.int32)
+        for s in range(n_seg):
+            copies = np.sort(rng.permutation(lens[s])[:TIE_COPIES])
+            pool[offs[s] + copies] = (4.0 + 0.5 * rng.randint(0, 4, 100)).astype(np.float32)
+            others = np.setdiff1d(np.arange(lens[s]), copies)
+            for f in range(n_rep):
+                row = rng.permutation(others)[:k]
+                a, b = pairs[(s + f) % len(pairs)]
+                row[a], row[b] = rng.permutation(copies)[:2]           # which copy sits in the lower slot is left to chance: the tie is by value
+                init[f * n_seg + s] = row
+        planted = [pairs[(s + f) % len(pairs)] for f in range(n_rep) for s in range(n_seg)]
+        rows, offs_out, seg_k = replicate_reference(np.arange(offs[-1], dtype=np.int32), offs, np.full(n_seg, k, np.int32), n_rep)
+        return dict(pool=pool, rows=rows, offs=offs_out, seg_k=seg_k, init=init, iters=iters, n_rep=n_rep, pairs=planted)
+    return make
+
+
+TIE_PAIR_CASES = [KmCase(f"tie_pairs_K{k}_it{it}", _tie_pairs(k, TIE_PAIRS[k], it, 7000 + k)) for k in (16, 64) for it in (1, 3)]
+
+# rows and initial code words on the lattice {0, 1, 2}^C: every product, sum and distance is a small integer, exact in float32 in any
+# order, so equal distances between DISTINCT code words are frequent and are true ties.  One row; 255, 256, 257 (the 256-row block and both
+# neighbours); 1 500.  K = 33 puts slot 32 alone in a third tile; the one-row segment starts from 33 equal code words.
+LATTICE_LENS = (1, 255, 256, 257, 1500)
+LATTICE_K = 33
+LATTICE_WIDTHS = (96, 100, 128, 70)          # km_assign_rank_kernel<25>, the matrix pipe, km_assign_rank_kernel<32>, km_assign_generic_kernel
+
+
+def _lattice(c):
+    def make():
+        rng = np.random.RandomState(3000 + c)
+        offs = _seg_offsets(LATTICE_LENS)
+        pool = rng.randint(0, 3, (int(offs[-1]), c)).astype(np.float32)
+        init = np.stack([rng.permutation(n)[:LATTICE_K] if n >= LATTICE_K else np.arange(LATTICE_K) % n for n in LATTICE_LENS])
+        return dict(pool=pool, offs=offs, seg_k=[LATTICE_K] * len(LATTICE_LENS), init=init, iters=1)
+    return make
+
+
+LATTICE_CASES = [KmCase(f"tie_lattice_C{c}", _lattice(c)) for c in LATTICE_WIDTHS]
+
+# rows = one offset of about 3 per feature plus noise of 1e-3: |x|^2 and |c|^2 are near 9 C, their ulp (2^-14 .. 2^-13) is of the size of the
+# differences between distances (2 C 1e-6), so the label of many rows is decided by where the three terms are rounded
+NEAR_TIE_SHAPES = [(100, 16, 1), (100, 16, 2), (100, 40, 1), (100, 40, 2), (96, 16, 1), (96, 40, 2), (128, 16, 1), (128, 40, 2), (70, 16, 1), (70, 40, 2)]
+
+
+def _near_tie(c, k, iters):
+    def make():
+        rng = np.random.RandomState(100 * c + k)
+        n = 1500
+        x = ((3.0 + 0.25 * rng.rand(c)) + 1e-3 * rng.randn(n, c)).astype(np.float32)
+        return dict(pool=x, seg_k=[k], init=rng.permutation(n)[:k].astype(np.int32)[None], iters=iters)
+    return make
+
+
+NEAR_TIE_CASES = [KmCase(f"near_tie_offset_C{c}_K{k}_it{it}", _near_tie(c, k, it)) for c, k, it in NEAR_TIE_SHAPES]
+
+KMEANS_CASES = (TAIL_CASES + [MOVING_CASE] + WIDTH_CASES + MFMA_CASES + GENERIC_CASES + STITCH_CASES + ASSIGN_CASES + TIE_PAIR_CASES + LATTICE_CASES
+                + NEAR_TIE_CASES)
+
+
+# 7. replicated lists at C = 100 (aoc_kmeans_segmented_rep with n_rep stated): replica f of base segment s is segment f * n_base + s, every
+# replica lists the same rows and starts from initial rows of its own
+def _rep_lists(rng, lens, n_rep, kmax, k=None, levels=None, iters=20, edit=None):
+    """Base segments of `lens` rows (a sorted random subset of a slightly larger pool), replicated n_rep times with min(k, len) clusters each, or
+    with the sticky per-replica levels; `edit(seg_k [n_rep, n_base])` may change cluster counts afterwards."""
+    lens = np.asarray(lens, np.int64)
+    offs = _seg_offsets(lens)
+    total, n_base = int(offs[-1]), len(lens)
+    pool = relu_gauss(rng, total + 30, 100)
+    rows = np.sort(rng.permutation(total + 30)[:total]).astype(np.int32)
+    if levels is None:
+        rows_out, offs_out, seg_k = replicate_reference(rows, offs, np.minimum(k, lens), n_rep)
+    else:
+        rows_out, offs_out, seg_k = replicate_levels_reference(rows, offs, n_rep, levels)
+    seg_k = seg_k.copy()
+    if edit is not None:
+        edit(seg_k.reshape(n_rep, n_base))
+    init = np.zeros((n_rep * n_base, kmax), np.int32)
+    for sr in range(n_rep * n_base):
+        init[sr, :seg_k[sr]] = rng.permutation(lens[sr % n_base])[:seg_k[sr]]
+    return dict(pool=pool, rows=rows_out, offs=offs_out, seg_k=seg_k, init=init, iters=iters, n_rep=n_rep)
+
+
+def _rep_uniform(lens, n_rep, k, seed, iters=20):
+    return lambda: _rep_lists(np.random.RandomState(seed), lens, n_rep, k, k=k, iters=iters)
+
+
+def _rep_levels(lens, n_rep, levels, seed):
+    return lambda: _rep_lists(np.random.RandomState(seed), lens, n_rep, max(levels), levels=levels)
+
+
+REP_BASE40_DEAD = (5, 20, 38)                       # base segments no replica clusters
+REP_BASE40_ONLY = {7: 0, 9: 1, 39: 2}               # base segment -> the one replica that clusters it
+
+
+def _rep_base40():
+    rng = np.random.RandomState(4040)
+    lens = np.concatenate([[1, 255, 256, 257], rng.randint(40, 500, 36)])
+
+    def edit(seg_k):
+        seg_k[:, list(REP_BASE40_DEAD)] = 0
+        for s, f in REP_BASE40_ONLY.items():
+            seg_k[np.arange(seg_k.shape[0]) != f, s] = 0
+    return _rep_lists(rng, lens, 3, 40, k=40, iters=5, edit=edit)
+
+
+def _rep_over_grid_cap():
+    """32 base segments (the most the replica kernel's LDS table holds), 22 short ones of one work item each among 10 of three or four: about
+    50 items per group, and 22 replicas at K = 40 are 11 groups of two -- more items than the 512 workgroups the grid is capped at."""
+    rng = np.random.RandomState(512)
+    lens = rng.permutation(np.concatenate([rng.randint(1, 40, 22), rng.randint(520, 860, 10)]))
+    return _rep_lists(rng, lens, 22, 40, k=40, iters=2)
+
+
+REP_TIE_PAIRS = tuple(p for p in TIE_PAIRS[64] if p[1] < 40)
+REP_CASES = [KmCase(f"rep_K40_n{n}", _rep_uniform((300, 257, 700, 41), n, 40, 4000 + n)) for n in (2, 3, 5)]
+REP_CASES += [KmCase("rep_levels_40_8_48", _rep_levels((700, 257, 300), 3, (40, 8, 48), 4048)),
+              KmCase("rep_K16_n13", _rep_uniform((300, 130, 600), 13, 16, 4013)),
+              KmCase("rep_K24_n7", _rep_uniform((300, 257, 130), 7, 24, 4024)),            # not asked for: <25, 2>, groups of 3 + 3 + 1, held to the oracle
+              KmCase("rep_base40", _rep_base40),
+              KmCase("rep_level_zero", _rep_levels((500, 300, 5, 0, 400), 4, (16, 0, 8), 4000)),
+              KmCase("rep_over_grid_cap", _rep_over_grid_cap),
+              KmCase("rep_tie_pairs", _tie_pairs(40, REP_TIE_PAIRS, 3, 7040, n_rep=3))]
+
+
+# ------------------------------------------------------------------------------------------ assignment rules and plans, restated
+def distances(dot, xs, cs):
+    """The float32 distance scipy compares, from the oracle's operands (oracle.kmeans.vq_parts): (-2 dot + |x|^2) + |c|^2, one rounding each."""
+    return (np.float32(-2.0) * dot + xs[:, None]) + cs[None, :]
+
+
+def lane_argmin(dist, in_lane="<", merge="lowest"):
+    """The argmin of the matrix-pipe kernels restated from the slot layout (slot_lane): per lane group a scan over its clusters, tiles in
+    order, with `in_lane` ("<" or "<="); then g0 | g1 and g2 | g3 exchange (xor 16), then the two winners (xor 32), and lane group 0's value
+    is the label.  merge: "lowest" = (d2 < low || (d2 == low && a2 < arg)); "highest" = a2 > arg; "keep" = the d2 == low clause dropped."""
+    n, k = dist.shape
+    kt = (k + 15) // 16
+    d = np.full((n, kt * 16), np.inf, np.float32)
+    d[:, :k] = dist
+    r = np.arange(n)
+    cand = []
+    for g in range(4):
+        slots = np.array([t * 16 + g * 4 + q for t in range(kt) for q in range(4)])
+        dg = d[:, slots]
+        pos = np.argmin(dg, 1) if in_lane == "<" else dg.shape[1] - 1 - np.argmin(dg[:, ::-1], 1)
+        low = dg[r, pos]
+        arg = np.where(np.isinf(low) & (in_lane == "<"), 0, slots[pos])      # low = INFINITY, arg = 0 is where a lane starts
+        cand.append((low, arg))
+
+    def exchange(mine, other):
+        take = other[0] < mine[0]
+        if merge != "keep":
+            take |= (other[0] == mine[0]) & ((other[1] < mine[1]) if merge == "lowest" else (other[1] > mine[1]))
+        return np.where(take, other[0], mine[0]), np.where(take, other[1], mine[1])
+    return exchange(exchange(cand[0], cand[1]), exchange(cand[2], cand[3]))[1].astype(np.int32)
+
+
+KM_REP_LDS_BUDGET = 78 * 1024
+KM_ASSIGN_GRID_CAP = 512
+KM_REP_SEG_LDS = 32
+
+
+def rep_plan(kmax, n_rep, n_base=1, base_rows=0):
+    """What aoc_kmeans_segmented_rep launches for the assignment at C = 100: the kernel, its KT, and for the replica kernel the code books that
+    fit one group (`fit`), the groups and the grid."""
+    kt = (kmax + 15) // 16
+    fixed = 4 * 16 * 116 * 4 + 4 * kmax * 4
+    per = (kt * 16 * 116 + kt * 16) * 4 + 256
+    fit = min(16, (KM_REP_LDS_BUDGET - fixed) // per)
+    gcap = KM_ASSIGN_GRID_CAP * 3 // 2 if kt == 1 else KM_ASSIGN_GRID_CAP
+    if n_rep <= 1 or fit < 2:
+        return dict(kernel="km_assign_mfma_kernel", kt=kt, fit=fit, gcap=gcap)
+    n_groups = (n_rep + fit - 1) // fit
+    n_grp = (n_rep + n_groups - 1) // n_groups
+    return dict(kernel="km_assign_mfma_rep_kernel", kt=kt, fit=fit, gcap=gcap, n_groups=n_groups, n_grp=n_grp,
+                groups=[min(n_grp, n_rep - g * n_grp) for g in range(n_groups)], grid=min((base_rows // 256 + n_base) * n_groups, gcap))
+
+
+def rep_case_plan(case):
+    """rep_plan of a replicated case, called as the GPU test calls it (rows_capacity = the replicated rows, the pool no shorter than the base
+    lists), plus `items`: the (group, base segment, block) work items in the order the persistent workgroups index them."""
+    d = case.data()
+    n_rep, n_base = d["n_rep"], len(d["seg_k"]) // d["n_rep"]
+    assert len(d["pool"]) * n_base >= len(d["rows"]) // n_rep
+    plan = rep_plan(d["kmax"], n_rep, n_base, len(d["rows"]) // n_rep)
+    live = (d["seg_k"].reshape(n_rep, n_base) > 0).any(0)
+    blocks = [(int(d["offs"][s + 1] - d["offs"][s]) + 255) // 256 if live[s] else 0 for s in range(n_base)]
+    plan["items"] = [(g, s, b) for g in range(plan.get("n_groups", 0)) for s in range(n_base) for b in range(blocks[s])]
+    return plan
 
 
 def is_fast(case):

@@ -189,8 +189,9 @@ def test_batched_cluster_chains_equal_single_chains(aoc):
 
 @pytest.mark.parametrize("levels,n_frames", [([16], 3), ([8, 16, 32], 1), ([8, 16, 32], 3), ([32], 7), ([64], 2)])
 def test_replica_fused_assignment_is_bit_identical(aoc, levels, n_frames):
-    """aoc_kmeans_segmented_rep (the rows of a block fetched once per GROUP of replicas: 6 / 3 / 1 code books per group at K <= 16 / 32 / 64,
-    so 7 replicas at K = 32 run as groups of 3 + 3 + 1 and K = 64 falls back to one replica per launch item) against the same replicated
+    """aoc_kmeans_segmented_rep (the rows of a block fetched once per GROUP of replicas: 6 / 3 / 2 / 1 code books per group at K <= 16 / 32 / 48 /
+    64, so 7 replicas at K = 32 run as groups of 3 + 3 + 1 and K = 64 falls back to one replica per launch item; K = 33 .. 48, groups of two, is
+    tests/test_gpu_kmeans_paths.py's) against the same replicated
     lists run with n_rep = 1: labels, code books and cluster sizes of all 20 Lloyd iterations' final state are equal bit for bit."""
     syn, ops = aoc.synthetic, aoc.ops
     cfg = syn.CONFIGS["cfg1"]

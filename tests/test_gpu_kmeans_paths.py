@@ -4,7 +4,10 @@ replicate (array_equal to torch-CPU / numpy references).  tests/test_kmeans_host
 and that every case reaches the path it is named for: the tail of a cluster beyond its 10 240 literal members (ties at both parities,
 binade crossings, more than four of them, a wrong binade prediction, the literal fallback), every width group of the fast path, the
 matrix-pipe assignment at one to four tiles of 16 clusters, the generic path at one to four features per lane, the stitch's ragged last
-block, more segments than the assignment's LDS table holds.
+block, more segments than the assignment's LDS table holds; exact distance ties decided by every step of the matrix-pipe argmin (inside a
+lane, across the xor-16 and xor-32 exchanges, the lower index in the higher lane group), true ties on an integer lattice at every assignment
+kernel, rows whose label hangs on where the distance is rounded; replicated lists in groups of 2 .. 5 code books, with more than 32 base
+segments, replicas and groups that skip a segment, ragged block ends, and more work items than workgroups.
 
 Every k-means and proxy case runs twice: once through aoc_amd.ops with a workspace of its own, once through ctypes in ONE workspace
 shared by the whole file that a differently shaped case has just used (what the frame pipeline does), into output buffers with a
@@ -94,12 +97,14 @@ def km_call(aoc, case, t, entry, ws):
     L, d = aoc._lib.lib(), case.data()
     S, kmax, C, cap = len(d["seg_k"]), d["kmax"], d["C"], len(d["rows"])
     cen, lab, cnt = Guarded(S * kmax * C, np.float32), Guarded(cap, np.int32), Guarded(S * kmax, np.int32)
-    tail = (ptr(t["rows"]), ptr(t["offs"]), ptr(t["seg_k"]), ptr(t["init"]), S, kmax, d["iters"], cap, cen.p, lab.p, cnt.p, ptr(ws), ws.numel(),
-            aoc.ops._stream())
-    if entry == "ex":
-        rc = L.aoc_kmeans_segmented_ex(ptr(t["pool"]), len(d["pool"]), C, *tail)
+    lists = (ptr(t["rows"]), ptr(t["offs"]), ptr(t["seg_k"]), ptr(t["init"]), S)
+    tail = (kmax, d["iters"], cap, cen.p, lab.p, cnt.p, ptr(ws), ws.numel(), aoc.ops._stream())
+    if entry == "rep":
+        rc = L.aoc_kmeans_segmented_rep(ptr(t["pool"]), len(d["pool"]), C, *lists, d["n_rep"], *tail)
+    elif entry == "ex":
+        rc = L.aoc_kmeans_segmented_ex(ptr(t["pool"]), len(d["pool"]), C, *lists, *tail)
     else:
-        rc = L.aoc_kmeans_segmented(ptr(t["pool"]), C, *tail)
+        rc = L.aoc_kmeans_segmented(ptr(t["pool"]), C, *lists, *tail)
     assert rc == OK
     torch.cuda.synchronize()
     return cen.get().reshape(S, kmax, C), lab.get(), cnt.get().reshape(S, kmax)
@@ -143,6 +148,27 @@ def test_kmeans_case_equals_the_oracle_bit_for_bit(aoc, on_device, case):
         third = km_call(aoc, case, t, "generic", ws)
         km_check(case, third, "aoc_kmeans_segmented (pool_rows = 0)")
         assert np.array_equal(first[0].view(np.int32), third[0].view(np.int32)), "the fast and the generic path differ"
+
+
+@pytest.mark.parametrize("case", kc.REP_CASES, ids=lambda c: c.name)
+def test_replicated_kmeans_equals_the_oracle_and_the_single_replica_chain(aoc, on_device, case):
+    """aoc_kmeans_segmented_rep with n_rep stated (km_assign_mfma_rep_kernel: <25, 3> in groups of two at K = 40 and 48, <25, 1> in groups of
+    up to six at K = 16; tests/test_kmeans_host.py holds every case to the plan and the edge it is named for) in the shared workspace a
+    differently shaped chain has just used, into guarded outputs, and the same lists with n_rep = 1 (km_assign_mfma_kernel).  Both are held
+    to the oracle, every replica of every case (rep_over_grid_cap too: its 22 replicas cost the oracle 1.5 s), and to each other: labels of
+    the live segments, all counts, code books as int32."""
+    d, t = case.data(), on_device(case)
+    assert d["n_rep"] > 1
+    scramble(aoc, case, on_device)
+    ws = shared_workspace(aoc._lib.lib().aoc_kmeans_workspace_bytes(len(d["rows"]), len(d["seg_k"]), d["kmax"], d["C"]))
+    fused = km_call(aoc, case, t, "rep", ws)
+    km_check(case, fused, f"n_rep = {d['n_rep']}")
+    plain = km_call(aoc, case, t, "ex", ws)
+    km_check(case, plain, "n_rep = 1")
+    live = np.concatenate([np.arange(d["offs"][s], d["offs"][s + 1]) for s in range(len(d["seg_k"])) if d["seg_k"][s] > 0])
+    assert np.array_equal(fused[1][live], plain[1][live]), "labels"
+    assert np.array_equal(fused[2], plain[2]), "counts"
+    assert np.array_equal(fused[0].view(np.int32), plain[0].view(np.int32)), "code books"
 
 
 # ------------------------------------------------------------------------------------------ proxies
