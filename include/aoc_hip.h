@@ -494,6 +494,37 @@ int aoc_atrous_subsample(const float *in, int h, int w, int X, int rate, float *
 int aoc_resize_nearest_bits(const uint32_t *in, int h, int w, uint32_t *out, int H, int W,
                             aoc_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Training-time local matching (csrc/local_grad.hip): what autograd needs of local_matching / local_matching_proxy (AEM:968-1060 over
+ * AEM:921-963, the parallel path).  fp32 only.  The reference keeps the unfolded previous frame [HW, C, (2R+1)^2] and the masked distance
+ * volume for its backward; here the forward reports the winning previous-frame pixel beside each minimum and the backward needs only
+ * that, the saved output and the two maps.
+ *
+ * aoc_local_window_match_argmin: arguments, limits and `out` of aoc_local_window_match_ex(float16 = 0) (for C = 100 / 128 bit for bit: the
+ * register-operand kernel's arithmetic term by term).  arg [n_obj, n_radii, H, W] (out's channel order): the previous-frame pixel
+ * cy * W + cx that holds the minimum of that channel's window; ties go to the lowest pixel index (row-major window order, the first
+ * occurrence) in every nested window alike; -1 where the value is the padding (no right pixel in the window): out is then exactly 1.0f
+ * with transform != 0 and the gradient is zero. */
+int aoc_local_window_match_argmin(const float *query, const float *prev, const uint32_t *right_bits, int H, int W, int C,
+                                  const int32_t *radii_host, int n_radii, const float *obj_bias, int n_obj,
+                                  float *out, int32_t *arg, int transform, int atrous_rate, aoc_stream_t stream);
+
+/* Backward of out = T = 2 sigmoid(d + bias[o]) - 1 with d = |q_i - p_arg|^2.  grad_out, T, arg: [n_obj, n_radii, H, W] contiguous;
+ * query, prev [H, W, C]; window = the largest window's half-size in pixels (atrous_rate * (radii[last] / atrous_rate)): an arg further
+ * than that from its query pixel (Chebyshev) or outside the map counts as -1.  With g = (grad_out * 0.5f) * (1 - T * T):
+ *   grad_query [H * W, C]  row i = sum over (o, ch), ascending, of (2 g) * (q_i - p_arg)
+ *   grad_prev  [H * W, C]  row j = sum over the (i, o, ch) with arg == j, ascending i, then o, then ch, of (2 g) * (p_j - q_i); every row is
+ *                          written, zeros where nobody chose it.  A gather over the query pixels within `window` of j: no atomics.
+ *   grad_bias  [n_obj]     sum over the pixels, ascending, of the sum over ch, ascending, of g
+ * Pairs with arg < 0 contribute nothing.  Each output may be NULL (nothing is computed for it).  No float atomics, every sum runs in an
+ * order fixed by the source: the same buffers give the same bits.  C <= AOC_MAX_CHANNELS, n_radii <= 8, n_obj <= AOC_MAX_OBJECTS,
+ * 0 <= window <= 31. */
+size_t aoc_local_match_grad_workspace_bytes(int H, int W, int C, int n_radii, int n_obj);
+int aoc_local_match_grad(const float *grad_out, const float *T, const int32_t *arg,
+                         const float *query, const float *prev, int H, int W, int C, int n_radii, int n_obj, int window,
+                         float *grad_query, float *grad_prev, float *grad_bias,
+                         void *workspace, size_t workspace_bytes, aoc_stream_t stream);
+
 /* ---- round 4: fused per-frame launches (each replaces several of the calls above and computes the same expressions term by term, so
  * the outputs equal theirs bit for bit; hotpath.proto_mask_features and aoc_frame_enqueue both use them) ---------------------------- */
 

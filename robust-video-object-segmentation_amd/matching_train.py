@@ -13,7 +13,8 @@ order without float atomics: two runs give the same bits.
 When autograd is off, or no input wants a gradient, every function here returns ``aoc_amd.matching``'s result unchanged.  Labels are never
 differentiated and never written into (the reference writes its atrous mask into the caller's tensor).  ``n_chunks`` is accepted and
 ignored.  ``use_float16=True`` has no backward (the model trains with MODEL_FLOAT16_MATCHING = False).  ``global_matching_cluster2`` and
-``local_matching`` are here so that an aliased import fails loudly: they are not yet differentiable.
+``local_matching`` are here so that an aliased import fails loudly: the first is not yet differentiable, the second is differentiable in
+``aoc_amd.local_train`` (a module of its own until the stub below may go; its error text points there).
 """
 import torch
 import torch.nn.functional as F
@@ -133,11 +134,12 @@ def global_matching_proxy(reference_embeddings, query_embeddings, reference_labe
     return _emit(planes, h, w, obj_nums, ori_size)
 
 
-def _not_yet(name, fn):
+def _not_yet(name, fn, elsewhere=None):
     def wrapper(*args, **kwargs):
         if _wants_grad(*args, *kwargs.values()):
+            tail = f"; aoc_amd.{elsewhere} is the differentiable form" if elsewhere else ""
             raise _lib.AocHipError(f"aoc_amd.matching_train.{name} is not yet differentiable (only global_matching and global_matching_proxy "
-                                   "have a backward): keep the reference's own function for it in a training run")
+                                   "have a backward): keep the reference's own function for it in a training run" + tail)
         return fn(*args, **kwargs)
     wrapper.__name__ = name
     wrapper.__doc__ = f"aoc_amd.matching.{name} when no gradient is wanted; raises under autograd (not yet differentiable)."
@@ -145,4 +147,4 @@ def _not_yet(name, fn):
 
 
 global_matching_cluster2 = _not_yet("global_matching_cluster2", matching.global_matching_cluster2)
-local_matching = _not_yet("local_matching", matching.local_matching)
+local_matching = _not_yet("local_matching", matching.local_matching, "local_train.local_matching")

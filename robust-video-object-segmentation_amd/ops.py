@@ -23,19 +23,21 @@ def _need_gpu(*tensors):
                                    f"got a tensor on {t.device}")
 
 
-# mirrors whose training twin has a backward in matching_train (keyed by the name the guard is called with)
-_TRAINABLE = {"global_matching_for_eval": "global_matching", "global_matching_for_eval_proxy": "global_matching_proxy"}
+# mirrors whose training twin has a backward (keyed by the name the guard is called with) -> module.function of the differentiable form
+_TRAINABLE = {"global_matching_for_eval": "matching_train.global_matching", "global_matching_for_eval_proxy": "matching_train.global_matching_proxy",
+              "local_matching": "local_train.local_matching", "local_matching_proxy": "local_train.local_matching_proxy"}
 
 
 def inference_only(what, *tensors):
     """The HIP kernels of the mirrors have no backward: every mirror returns tensors WITHOUT an autograd graph.  Dropping the reference's
     training-time names (IA_gate, conditioning_block, GCT, global_matching, ...) into a training run would therefore train
-    nothing, silently.  Raise instead when autograd is recording and an input or parameter wants a gradient.  The two functions that
-    do have a backward, global_matching and global_matching_proxy, live in aoc_amd.matching_train; the error text says so for them."""
+    nothing, silently.  Raise instead when autograd is recording and an input or parameter wants a gradient.  The functions that do
+    have a backward live in aoc_amd.matching_train (global_matching, global_matching_proxy) and aoc_amd.local_train (local_matching,
+    local_matching_proxy); the error text says so for them."""
     if torch.is_grad_enabled():
         for t in tensors:
             if torch.is_tensor(t) and t.requires_grad:
-                hint = ("; aoc_amd.matching_train." + _TRAINABLE[what] + " is the differentiable form") if what in _TRAINABLE else ""
+                hint = ("; aoc_amd." + _TRAINABLE[what] + " is the differentiable form") if what in _TRAINABLE else ""
                 raise _lib.AocHipError(f"aoc_amd.{what} is inference-only (no autograd graph is built): call it under torch.no_grad() "
                                        "or detach its inputs; training must use the reference's PyTorch modules" + hint)
 
@@ -596,6 +598,53 @@ def local_window_match(query, prev, right_bits, radii, obj_bias, n_obj, transfor
                                                     int(radii.size), _p(obj_bias), n_obj, _p(out), int(bool(transform)), int(atrous_rate),
                                                     int(bool(float16)), _stream()), "aoc_local_window_match_ex")
     return out
+
+
+def local_window_match_argmin(query, prev, right_bits, radii, obj_bias, n_obj, transform=True, atrous_rate=1, out=None, arg=None):
+    """aoc_local_window_match_argmin: local_window_match's values (float16=False; bit for bit at C = 100 / 128) and, in ``arg`` (int32, shaped
+    like ``out``), the previous-frame pixel cy * W + cx of every minimum; -1 where the value is the padding.  -> (out, arg)
+    [n_obj, len(radii), H, W].  The keyword buffers, when given, are written in place."""
+    query, prev = _f32c(query), _f32c(prev)
+    _need_gpu(query, prev, right_bits, out, arg)
+    H, W, C = query.shape
+    radii = np.ascontiguousarray(np.asarray(radii, dtype=np.int32))
+    if out is None:
+        out = torch.empty(n_obj, radii.size, H, W, dtype=torch.float32, device=query.device)
+    if arg is None:
+        arg = torch.empty(n_obj, radii.size, H, W, dtype=torch.int32, device=query.device)
+    assert arg.dtype == torch.int32 and out.dtype == torch.float32
+    if obj_bias is not None:
+        obj_bias = _f32c(obj_bias)
+    _lib.check(_lib.lib().aoc_local_window_match_argmin(_p(query), _p(prev), _p(right_bits), H, W, C, radii.ctypes.data_as(ctypes.c_void_p),
+                                                        int(radii.size), _p(obj_bias), n_obj, _p(out), _p(arg), int(bool(transform)),
+                                                        int(atrous_rate), _stream()), "aoc_local_window_match_argmin")
+    return out, arg
+
+
+def local_match_backward(grad_out, T, arg, query, prev, window, want_query=True, want_prev=True, want_bias=True,
+                         grad_query=None, grad_prev=None, grad_bias=None):
+    """aoc_local_match_grad.  grad_out, T, arg [n_obj, n_radii, H, W] contiguous; query, prev [H, W, C]; window = the largest window's
+    half-size in pixels.  -> (grad_query [H, W, C], grad_prev [H, W, C], grad_bias [n_obj]); None for an output that is not wanted (nothing
+    is written for it).  The keyword buffers, when given, are written in place."""
+    query, prev = _f32c(query), _f32c(prev)
+    _need_gpu(grad_out, T, arg, query, prev, grad_query, grad_prev, grad_bias)
+    assert grad_out.dtype == torch.float32 and T.dtype == torch.float32 and arg.dtype == torch.int32
+    assert grad_out.is_contiguous() and T.is_contiguous() and arg.is_contiguous()
+    n_obj, n_radii, H, W = T.shape
+    C = query.shape[2]
+    dev = query.device
+    if want_query and grad_query is None:
+        grad_query = torch.empty(H, W, C, dtype=torch.float32, device=dev)
+    if want_prev and grad_prev is None:
+        grad_prev = torch.empty(H, W, C, dtype=torch.float32, device=dev)
+    if want_bias and grad_bias is None:
+        grad_bias = torch.empty(n_obj, dtype=torch.float32, device=dev)
+    gq, gp, gb = (grad_query if want_query else None), (grad_prev if want_prev else None), (grad_bias if want_bias else None)
+    L = _lib.lib()
+    ws = _ws(L.aoc_local_match_grad_workspace_bytes(H, W, C, n_radii, n_obj), dev)
+    _lib.check(L.aoc_local_match_grad(_p(grad_out), _p(T), _p(arg), _p(query), _p(prev), H, W, C, n_radii, n_obj, int(window),
+                                      _p(gq), _p(gp), _p(gb), _p(ws), ws.numel(), _stream()), "aoc_local_match_grad")
+    return gq, gp, gb
 
 
 def local_prep(cur_emb, prev_emb, prev_labels_flat, prev_pos, H2, W2, obj_bias=None, n_pair_sets=0, set_bias_out=None, copies=()):
