@@ -525,6 +525,62 @@ int aoc_local_match_grad(const float *grad_out, const float *T, const int32_t *a
                          float *grad_query, float *grad_prev, float *grad_bias,
                          void *workspace, size_t workspace_bytes, aoc_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Training-time cluster matching (csrc/cluster_grad.hip): what autograd needs of global_matching_cluster2 (AEM:405-478 over AEM:231-332;
+ * matching.py:1324-1404 over 506-640).  Set 0 of an object, the k-means code book, is a constant (torch.from_numpy, AEM:279); set 1,
+ * centroid_avg (AEM:280), is a differentiable mean of reference rows.  Labels, the assignment and the drawn rows carry no gradient.
+ *
+ * aoc_proxy_set_match_argmin: aoc_proxy_corr_min (AEM:92-110, 316-319; same arguments, sets as HOST arrays, transform 0 or 1) plus arg,
+ * int32, addressed like out: arg[i*out_pixel_stride + set_out_offset[s]] = the slot WITHIN the set (0 .. set_size[s] - 1) of the minimum;
+ * ties go to the lowest slot (torch.min's choice on a tie is one of them); -1 where the set is empty or all-ignored (+inf norms): the
+ * value is then AOC_PAD_DISTANCE and T exactly 1.0f.  out holds bit for bit what aoc_proxy_corr_min writes for the same arguments (the
+ * same fp32 MFMA sequence and the same norm sums; a slot index rides beside each minimum).  C as aoc_proxy_corr_min (a multiple of 4,
+ * 4 .. AOC_MAX_CHANNELS), set sizes 0 .. AOC_MAX_CLUSTERS (beyond: AOC_ERR_UNSUPPORTED), any number of sets (a frame has
+ * 2 * levels * objects of them; 64 go into one launch).  No workspace.  proxy_sqnorm = NULL is the slow form: every lane sums |p|^2 over
+ * all C again for every tile of 16 query pixels. */
+int aoc_proxy_set_match_argmin(const float *query, int64_t m, int C,
+                               const float *proxies, const float *proxy_sqnorm, int n_proxy,
+                               int n_set, const int32_t *set_begin_host, const int32_t *set_size_host,
+                               const int64_t *set_out_offset_host, const float *set_bias,
+                               float *out, int32_t *arg, int64_t out_pixel_stride, int transform, aoc_stream_t stream);
+
+/* The backward of the min over sets (AEM:109 / 319) followed by the proto-mask transform (AEM:467-468).  grad_out, T (the saved
+ * transformed output) and arg are addressed as in the forward ([i*pixel_stride + set_out_offset[s]]); query [m, C]; proxies [n_proxy, C];
+ * set_bias_index [n_set], HOST: the element of grad_bias the set's bias came from (its object).  With g = (grad_out * 0.5f) * (1 - T*T) and
+ * p* = proxies[set_begin[s] + arg] of (pixel i, set s):
+ *   grad_query   [m, C]       row i = sum over the sets, ascending, of (2 g) * (q_i - p*)
+ *   grad_proxies [n_proxy, C] row r = 2 (p_r * sum g - sum g q_i) over the pairs that chose r; EVERY row is written, with zeros where nobody
+ *                             chose it or it lies outside every set
+ *   grad_bias    [n_bias]     sum of g over the pixels and over the sets that name that element
+ * Pairs with arg < 0 (or >= set_size) contribute nothing.  Each output may be NULL (nothing is computed for it).  Few rows, every one of
+ * them hot: the pixels are cut into n_chunk = min(128, ceil(m / 32)) contiguous chunks; a workgroup adds g q_i of one (chunk, set, 32 slots)
+ * in pixel order into LDS rows, one thread per channel; a second pass adds the chunks in ascending (set, chunk) order per proxy row.  No
+ * float atomics, every sum in an order fixed by (m, sets) alone: the same buffers give the same bits.
+ * workspace: align256(n_slot * n_chunk * (C + 1) * 4 + 16) + align256(n_slot * 4 + 16) bytes, n_slot = the sum of the set sizes: bounded
+ * in m (at most 128 chunks), it never holds a [m, n_proxy, C] term.  Only needed when grad_proxies or grad_bias is wanted.
+ * C and set sizes as the forward; set_bias_index may be NULL when grad_bias is. */
+size_t aoc_proxy_set_match_grad_workspace_bytes(int64_t m, int C, int64_t n_slot);
+int aoc_proxy_set_match_grad(const float *grad_out, const float *T, const int32_t *arg, int64_t pixel_stride,
+                             const float *query, int64_t m, int C, const float *proxies, int n_proxy,
+                             int n_set, const int32_t *set_begin_host, const int32_t *set_size_host,
+                             const int64_t *set_out_offset_host, const int32_t *set_bias_index_host, int n_bias,
+                             float *grad_query, float *grad_proxies, float *grad_bias,
+                             void *workspace, size_t workspace_bytes, aoc_stream_t stream);
+
+/* The backward of aoc_build_proxies' set 1 (AEM:280, centroid_avg: cluster j of segment s is the mean of the rows fg[p] of the GLOBAL
+ * kept-row array over the segment-local p with label == j; the reference's indexing, reproduced as is).  grad_proxies
+ * [n_seg, 2, kmax, C] (only [:, 1] is read); fg_rows, n_fg (device), seg_offsets [n_seg + 1], seg_k [n_seg] and the packed labels
+ * [rows_capacity] as aoc_build_proxies takes them.  grad_pool [pool_rows, C]:
+ *   row fg_rows[p] = sum over the segments s with length > p, ascending, of grad_proxies[s, 1, labels_s[p]] / count_s(labels_s[p]),
+ * count_s(j) = the number of p in segment s with label j (what the mean was divided by); every other row is zero.  A gather, one wave per
+ * kept position: a row shared by several segments needs neither atomics nor ordering.  Multi-level segment lists
+ * (n_seg = levels * objects, aoc_kmeans_replicate_levels) are segments like any other.  workspace: the counts, [n_seg, kmax] int32. */
+size_t aoc_centroid_avg_grad_workspace_bytes(int n_seg, int kmax);
+int aoc_centroid_avg_grad(const float *grad_proxies, int C, const int32_t *fg_rows, const int32_t *n_fg,
+                          const int32_t *seg_offsets, const int32_t *seg_k, const int32_t *labels,
+                          int n_seg, int kmax, int64_t rows_capacity, float *grad_pool, int64_t pool_rows,
+                          void *workspace, size_t workspace_bytes, aoc_stream_t stream);
+
 /* ---- round 4: fused per-frame launches (each replaces several of the calls above and computes the same expressions term by term, so
  * the outputs equal theirs bit for bit; hotpath.proto_mask_features and aoc_frame_enqueue both use them) ---------------------------- */
 

@@ -128,6 +128,11 @@ SIGNATURES = {
     "aoc_local_window_match_argmin": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp]),
     "aoc_local_match_grad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "aoc_local_match_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "aoc_proxy_set_match_argmin": (_i, [_vp, _i64, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _vp]),
+    "aoc_proxy_set_match_grad_workspace_bytes": (_sz, [_i64, _i, _i64]),
+    "aoc_proxy_set_match_grad": (_i, [_vp, _vp, _vp, _i64, _vp, _i64, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "aoc_centroid_avg_grad_workspace_bytes": (_sz, [_i, _i]),
+    "aoc_centroid_avg_grad": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _i64, _vp, _sz, _vp]),
 }
 
 STATUS = {0: "AOC_OK", -1: "AOC_ERR_INVALID_ARG", -2: "AOC_ERR_WORKSPACE", -3: "AOC_ERR_LAUNCH", -4: "AOC_ERR_UNSUPPORTED"}

@@ -13,8 +13,8 @@ order without float atomics: two runs give the same bits.
 When autograd is off, or no input wants a gradient, every function here returns ``aoc_amd.matching``'s result unchanged.  Labels are never
 differentiated and never written into (the reference writes its atrous mask into the caller's tensor).  ``n_chunks`` is accepted and
 ignored.  ``use_float16=True`` has no backward (the model trains with MODEL_FLOAT16_MATCHING = False).  ``global_matching_cluster2`` and
-``local_matching`` are here so that an aliased import fails loudly: the first is not yet differentiable, the second is differentiable in
-``aoc_amd.local_train`` (a module of its own until the stub below may go; its error text points there).
+``local_matching`` are here so that an aliased import fails loudly: they are differentiable in ``aoc_amd.cluster_train`` and
+``aoc_amd.local_train`` (modules of their own until the stubs below may go; their error texts point there).
 """
 import torch
 import torch.nn.functional as F
@@ -146,5 +146,5 @@ def _not_yet(name, fn, elsewhere=None):
     return wrapper
 
 
-global_matching_cluster2 = _not_yet("global_matching_cluster2", matching.global_matching_cluster2)
+global_matching_cluster2 = _not_yet("global_matching_cluster2", matching.global_matching_cluster2, "cluster_train.global_matching_cluster2")
 local_matching = _not_yet("local_matching", matching.local_matching, "local_train.local_matching")

@@ -25,15 +25,16 @@ def _need_gpu(*tensors):
 
 # mirrors whose training twin has a backward (keyed by the name the guard is called with) -> module.function of the differentiable form
 _TRAINABLE = {"global_matching_for_eval": "matching_train.global_matching", "global_matching_for_eval_proxy": "matching_train.global_matching_proxy",
-              "local_matching": "local_train.local_matching", "local_matching_proxy": "local_train.local_matching_proxy"}
+              "local_matching": "local_train.local_matching", "local_matching_proxy": "local_train.local_matching_proxy",
+              "global_matching_for_eval_cluster": "cluster_train.global_matching_cluster2"}
 
 
 def inference_only(what, *tensors):
     """The HIP kernels of the mirrors have no backward: every mirror returns tensors WITHOUT an autograd graph.  Dropping the reference's
     training-time names (IA_gate, conditioning_block, GCT, global_matching, ...) into a training run would therefore train
     nothing, silently.  Raise instead when autograd is recording and an input or parameter wants a gradient.  The functions that do
-    have a backward live in aoc_amd.matching_train (global_matching, global_matching_proxy) and aoc_amd.local_train (local_matching,
-    local_matching_proxy); the error text says so for them."""
+    have a backward live in aoc_amd.matching_train (global_matching, global_matching_proxy), aoc_amd.local_train (local_matching,
+    local_matching_proxy) and aoc_amd.cluster_train (global_matching_cluster2); the error text says so for them."""
     if torch.is_grad_enabled():
         for t in tensors:
             if torch.is_tensor(t) and t.requires_grad:
@@ -428,6 +429,81 @@ def proxy_match_backward(grad_out, T, pixel_stride, obj_stride, query_flat, prox
     _lib.check(L.aoc_proxy_match_grad(_p(grad_out), _p(T), int(pixel_stride), int(obj_stride), _p(query_flat), m, C, _p(proxies), n_obj,
                                       _p(gq), _p(gp), _p(gb), _p(ws), ws.numel(), _stream()), "aoc_proxy_match_grad")
     return gq, gp, gb
+
+
+def _set_arrays(set_begin, set_size, set_out_offset):
+    sb = np.ascontiguousarray(np.asarray(set_begin, dtype=np.int32))
+    ss = np.ascontiguousarray(np.asarray(set_size, dtype=np.int32))
+    so = np.ascontiguousarray(np.asarray(set_out_offset, dtype=np.int64))
+    assert ss.size == sb.size and so.size == sb.size
+    return sb, ss, so
+
+
+def proxy_set_match_argmin(query_flat, proxies, proxy_sqnorm, set_begin, set_size, set_out_offset, set_bias, out, arg, out_pixel_stride,
+                           transform=True):
+    """aoc_proxy_set_match_argmin: proxy_corr_min's values (bit for bit) and, in ``arg`` (int32, addressed like ``out``), the slot within the
+    set of every minimum (ties: the lowest); -1 where the set is empty or all-ignored."""
+    query_flat = _f32c(query_flat)
+    proxies = _f32c(proxies)
+    proxy_sqnorm = _f32c(proxy_sqnorm) if proxy_sqnorm is not None else None
+    _need_gpu(query_flat, proxies, proxy_sqnorm, out, arg, set_bias)
+    assert out.dtype == torch.float32 and arg.dtype == torch.int32
+    m, C = query_flat.shape
+    sb, ss, so = _set_arrays(set_begin, set_size, set_out_offset)
+    if set_bias is not None:
+        set_bias = _f32c(set_bias)
+        assert set_bias.numel() == sb.size
+    vp = ctypes.c_void_p
+    _lib.check(_lib.lib().aoc_proxy_set_match_argmin(_p(query_flat), m, C, _p(proxies), _p(proxy_sqnorm), proxies.shape[0], sb.size,
+                                                     sb.ctypes.data_as(vp), ss.ctypes.data_as(vp), so.ctypes.data_as(vp), _p(set_bias), _p(out), _p(arg),
+                                                     int(out_pixel_stride), int(bool(transform)), _stream()), "aoc_proxy_set_match_argmin")
+    return out, arg
+
+
+def proxy_set_match_backward(grad_out, T, arg, pixel_stride, query_flat, proxies, set_begin, set_size, set_out_offset, set_bias_index, n_bias,
+                             want_query=True, want_proxies=True, want_bias=True, grad_query=None, grad_proxies=None, grad_bias=None):
+    """aoc_proxy_set_match_grad.  grad_out, T and arg are addressed as [i * pixel_stride + set_out_offset[s]] from their data pointers;
+    set_bias_index[s] = the element of grad_bias set s belongs to.  -> (grad_query [m, C], grad_proxies [n_proxy, C], grad_bias [n_bias]);
+    None for an output that is not wanted.  The keyword buffers, when given, are written in place."""
+    query_flat = _f32c(query_flat)
+    proxies = _f32c(proxies)
+    _need_gpu(grad_out, T, arg, query_flat, proxies, grad_query, grad_proxies, grad_bias)
+    assert grad_out.dtype == torch.float32 and T.dtype == torch.float32 and arg.dtype == torch.int32
+    m, C = query_flat.shape
+    dev = query_flat.device
+    sb, ss, so = _set_arrays(set_begin, set_size, set_out_offset)
+    si = np.ascontiguousarray(np.asarray(set_bias_index, dtype=np.int32))
+    assert si.size == sb.size
+    if want_query and grad_query is None:
+        grad_query = torch.empty(m, C, dtype=torch.float32, device=dev)
+    if want_proxies and grad_proxies is None:
+        grad_proxies = torch.empty(proxies.shape[0], C, dtype=torch.float32, device=dev)
+    if want_bias and grad_bias is None:
+        grad_bias = torch.empty(int(n_bias), dtype=torch.float32, device=dev)
+    gq, gp, gb = (grad_query if want_query else None), (grad_proxies if want_proxies else None), (grad_bias if want_bias else None)
+    L = _lib.lib()
+    ws = _ws(L.aoc_proxy_set_match_grad_workspace_bytes(m, C, int(ss.sum())) if (want_proxies or want_bias) else 0, dev)
+    vp = ctypes.c_void_p
+    _lib.check(L.aoc_proxy_set_match_grad(_p(grad_out), _p(T), _p(arg), int(pixel_stride), _p(query_flat), m, C, _p(proxies), proxies.shape[0], sb.size,
+                                          sb.ctypes.data_as(vp), ss.ctypes.data_as(vp), so.ctypes.data_as(vp), si.ctypes.data_as(vp), int(n_bias),
+                                          _p(gq), _p(gp), _p(gb), _p(ws), ws.numel(), _stream()), "aoc_proxy_set_match_grad")
+    return gq, gp, gb
+
+
+def centroid_avg_backward(grad_proxies, fg_rows, n_fg, seg_offsets, seg_k, labels, pool_rows, grad_pool=None):
+    """aoc_centroid_avg_grad: grad_proxies [n_seg, 2, kmax, C] (only [:, 1] is read) pulled back through build_proxies' means
+    -> grad_pool [pool_rows, C]; n_fg is the device element that holds the number of kept rows (LabelPrep.counts[n_obj:])."""
+    grad_proxies = _f32c(grad_proxies)
+    _need_gpu(grad_proxies, fg_rows, n_fg, seg_offsets, seg_k, labels, grad_pool)
+    n_seg, two, kmax, C = grad_proxies.shape
+    assert two == 2 and seg_k.numel() == n_seg and seg_offsets.numel() == n_seg + 1
+    if grad_pool is None:
+        grad_pool = torch.empty(int(pool_rows), C, dtype=torch.float32, device=grad_proxies.device)
+    L = _lib.lib()
+    ws = _ws(L.aoc_centroid_avg_grad_workspace_bytes(n_seg, kmax), grad_proxies.device)
+    _lib.check(L.aoc_centroid_avg_grad(_p(grad_proxies), C, _p(fg_rows), _p(n_fg), _p(seg_offsets), _p(seg_k), _p(labels), n_seg, kmax,
+                                       int(labels.numel()), _p(grad_pool), int(pool_rows), _p(ws), ws.numel(), _stream()), "aoc_centroid_avg_grad")
+    return grad_pool
 
 
 class SplitRows:
