@@ -620,7 +620,12 @@ class CalibrationGates(nn.Module):
                tuple(d[n].data_ptr() for d, n in self._param_slots if d[n] is not None))
         if not hasattr(self, "_batches"):
             self._batches = {}
+        base = key
         cached = self._batches.get(slot)                 # one set of output buffers per caller slot (e.g. per sequence in flight)
+        if cached is not None and cached[1].converted:
+            # parameters that are not contiguous float32 (module.double(), .half()) are read from converted COPIES: their storage says nothing
+            # about an in-place update, so their versions join the key (only then: the float32 path pays one attribute read)
+            key = key + tuple(d[n]._version for d, n in self._param_slots if d[n] is not None)
         if cached is None or cached[0] != key:
             entries = []
             for (name, c, hh, ww, extra), x in zip(self.plan(0, 0), activations):
@@ -634,7 +639,10 @@ class CalibrationGates(nn.Module):
                                            mod.CL_3.mlp_layer.weight, mod.CL_3.mlp_layer.bias, k_rank)))
                 else:
                     entries.append((1 if extra else 0, x, (mod.IA.weight, mod.IA.bias)))
-            cached = (key, ops.GateBatch(entries, activations[0].shape[0], attention_head.shape[1]))
+            batch = ops.GateBatch(entries, activations[0].shape[0], attention_head.shape[1])
+            if batch.converted:
+                base = base + tuple(d[n]._version for d, n in self._param_slots if d[n] is not None)
+            cached = (base, batch)
             self._batches[slot] = cached
         return cached[1](attention_head, probes)
 

@@ -3,6 +3,18 @@ and passes raw pointers + the current HIP stream to libaoc_hip.so.  PyTorch is p
 (device memory and streams); every computation happens in the HIP library.
 
 All functions require CUDA(HIP) tensors and raise otherwise -- there is no CPU path.
+
+The tensor contract (the library reads bare pointers; tests/ops_contract_cases.py holds every public callable to it):
+  * INPUTS are converted: a float input of another dtype or a non-contiguous view becomes a contiguous float32 copy (_f32c), an integer
+    list (rows, offsets, counts, label bits, label maps) a contiguous int32 copy (_i32c; no range check, see there).  The copies are bound
+    to names that live until the library call has been made.  Inputs the library addresses with the CALLER's strides (grad_out / T / arg of
+    the dense and proxy backward calls, `dis` of fg2bg_min with explicit strides) cannot be converted and are checked like outputs.
+  * Caller-provided OUTPUTS (out=, arg=, grad_*=, outs=, the tables of cluster_chain, the SplitRows of split_rows(out=...)) are never
+    converted behind the caller's back: contiguous, the exact dtype and the exact shape (_out) -- or, for a destination addressed with
+    explicit strides from its data pointer, contiguous, the exact dtype and at least the elements the strides reach (_span).  Anything else
+    raises ValueError (AssertionError in the per-frame calls FrameCall / GateBatch, which assert instead of converting) BEFORE anything is
+    enqueued, so the buffer is untouched.
+  * Every address leaves through _p (ctypes arguments) or _addr (structure fields, pointer arrays), given a NAME, never a call expression.
 """
 import ctypes
 import os
@@ -47,6 +59,13 @@ def _p(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _addr(t):
+    """_p's sibling for the fields of ctypes structures and for pointer arrays: the integer address (None stays None).  _p and _addr are the
+    only two places where a tensor's address leaves for the library; the tensor they are given must be bound to a name that lives until
+    the library call has been made (never a temporary: a copy freed right after its address is taken can be handed out again)."""
+    return t.data_ptr() if t is not None else None
+
+
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 _RAW_DEVICE = getattr(torch._C, "_cuda_getDevice", None)
 
@@ -64,6 +83,41 @@ def _f32c(t):
     if t.dtype != torch.float32:
         t = t.float()
     return t.contiguous()
+
+
+def _i32c(t):
+    """int32 + contiguous: the integer lists of the C ABI (rows, offsets, counts, label bits) are int32, torch's default integer is int64.
+    The conversion does NOT check the range: row indices and counts are below 2^31 by construction (a pool of 2^31 rows does not fit the
+    device), label bits are 32-bit patterns, and a check would need a device synchronisation."""
+    if t.dtype != torch.int32:
+        t = t.to(torch.int32)
+    return t.contiguous()
+
+
+def _out(what, t, shape, dtype=torch.float32):
+    """A caller-provided output is written in place through its bare pointer and is never converted behind the caller's back: ValueError
+    unless it is contiguous and has exactly this dtype and shape."""
+    if t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what} must be a contiguous {str(dtype).replace('torch.', '')} tensor of shape {tuple(shape)}, got "
+                         f"{'a' if t.is_contiguous() else 'a non-contiguous'} {str(t.dtype).replace('torch.', '')} tensor of shape {tuple(t.shape)}")
+    return t
+
+
+def _span(what, t, need, dtype=torch.float32):
+    """A buffer the library addresses with explicit strides from its data pointer (a channel slice of a larger tensor, the tail of a table):
+    ValueError unless it is contiguous, has this dtype and holds at least `need` elements counted from its first."""
+    if t.dtype != dtype or not t.is_contiguous() or t.numel() < int(need):
+        raise ValueError(f"{what} must be a contiguous {str(dtype).replace('torch.', '')} tensor of at least {int(need)} elements, got "
+                         f"{'a' if t.is_contiguous() else 'a non-contiguous'} {str(t.dtype).replace('torch.', '')} tensor of {t.numel()}")
+    return t
+
+
+def _prep_lists(prep):
+    """The six int32 lists of a LabelPrep, converted where a caller built them in another integer type
+    -> (right_bits, wrong_bits, fg_rows, obj_rows, counts, obj_offsets); None for a list the caller left out (the exact-fp32 dense calls read
+    three of the six)."""
+    return tuple(_i32c(t) if t is not None else None
+                 for t in (getattr(prep, f, None) for f in ("right_bits", "wrong_bits", "fg_rows", "obj_rows", "counts", "obj_offsets")))
 
 
 def _ws(nbytes, device):
@@ -109,6 +163,7 @@ def label_prep(labels_flat):
 
 def kmeans_plan(counts, n_seg, cluster_num):
     _need_gpu(counts)
+    counts = _i32c(counts)
     seg_k = torch.empty(n_seg, dtype=torch.int32, device=counts.device)
     _lib.check(_lib.lib().aoc_kmeans_plan(_p(counts), n_seg, int(cluster_num), _p(seg_k), _stream()), "aoc_kmeans_plan")
     return seg_k
@@ -152,7 +207,7 @@ def kmeans_segmented(pool, rows, seg_offsets, seg_k, init_rows, kmax, iters=20, 
     labels = torch.empty(cap, dtype=torch.int32, device=dev)
     ccounts = torch.empty(n_seg, kmax, dtype=torch.int32, device=dev)
     ws = _ws(L.aoc_kmeans_workspace_bytes(cap, n_seg, kmax, C), dev)
-    init_rows = init_rows.to(torch.int32).contiguous()
+    rows, seg_offsets, seg_k, init_rows = _i32c(rows), _i32c(seg_offsets), _i32c(seg_k), _i32c(init_rows)
     _lib.check(L.aoc_kmeans_segmented_rep(_p(pool), pool.shape[0], C, _p(rows), _p(seg_offsets), _p(seg_k), _p(init_rows), n_seg, int(n_rep), kmax,
                                           int(iters), cap, _p(centroids), _p(labels), _p(ccounts), _p(ws), ws.numel(), _stream()),
                "aoc_kmeans_segmented_rep")
@@ -162,6 +217,7 @@ def kmeans_segmented(pool, rows, seg_offsets, seg_k, init_rows, kmax, iters=20, 
 def kmeans_replicate(rows, seg_offsets, seg_k, n_rep, rows_capacity=None):
     """Segment lists replicated n_rep times (aoc_kmeans_replicate) -> (rows [n_rep*cap], seg_offsets [n_rep*S+1], seg_k [n_rep*S])."""
     _need_gpu(rows, seg_offsets, seg_k)
+    rows, seg_offsets, seg_k = _i32c(rows), _i32c(seg_offsets), _i32c(seg_k)
     n_seg = seg_k.numel()
     cap = int(rows.numel() if rows_capacity is None else rows_capacity)
     dev = rows.device
@@ -177,6 +233,7 @@ def kmeans_replicate_levels(rows, seg_offsets, n_seg, n_rep, levels, rows_capaci
     """aoc_kmeans_replicate_levels: n_rep replicas of the segment lists, replica f clustering at K = levels[f % len(levels)] with the
     sticky rule of AEM:268 applied on the device -> (rows [n_rep*cap], seg_offsets [n_rep*S+1], seg_k [n_rep*S])."""
     _need_gpu(rows, seg_offsets)
+    rows, seg_offsets = _i32c(rows), _i32c(seg_offsets)
     cap = int(rows.numel() if rows_capacity is None else rows_capacity)
     dev = rows.device
     lv = np.ascontiguousarray(np.asarray(levels, dtype=np.int32))
@@ -192,6 +249,7 @@ def build_proxies(pool, fg_rows, seg_offsets, seg_k, labels, centroids):
     """AEM:280-282 -> (proxies [S,2,kmax,C], proxy_sqnorm [S,2,kmax]); +inf norm = absent proxy."""
     pool = _f32c(pool)
     _need_gpu(pool, fg_rows, seg_offsets, seg_k, labels, centroids)
+    fg_rows, seg_offsets, seg_k, labels, centroids = _i32c(fg_rows), _i32c(seg_offsets), _i32c(seg_k), _i32c(labels), _f32c(centroids)
     n_seg, kmax, C = centroids.shape
     L = _lib.lib()
     proxies = torch.empty(n_seg, 2, kmax, C, dtype=torch.float32, device=pool.device)
@@ -222,6 +280,7 @@ def proxy_corr_min(query_flat, proxies, proxy_sqnorm, set_begin, set_size, set_o
     if set_bias is not None:
         set_bias = _f32c(set_bias)
         assert set_bias.numel() == n_set
+    _span("proxy_corr_min: out", out, (m - 1) * int(out_pixel_stride) + int(so.max()) + 1 if n_set and m else 0)
     vp = ctypes.c_void_p
     fn = _lib.lib().aoc_proxy_corr_min_f16 if float16 else _lib.lib().aoc_proxy_corr_min
     _lib.check(fn(_p(query_flat), m, C, _p(proxies), _p(proxy_sqnorm), proxies.shape[0], n_set,
@@ -275,9 +334,9 @@ def proxy_corr_min_batched(frames, set_begin, set_size, set_out_offset, transfor
         b = _f32c(b) if b is not None else None
         _need_gpu(q, p, sq, b, out)
         assert q.shape == (m, C) and p.shape == (n_proxy, C) and (b is None or b.numel() == n_set)
-        keep.append((q, p, sq, b))
-        arr[i] = _CorrFrame(q.data_ptr(), p.data_ptr(), sq.data_ptr() if sq is not None else None, b.data_ptr() if b is not None else None,
-                            out.data_ptr())
+        _span("proxy_corr_min_batched: out", out, int(so.max()) + m if n_set else 0)
+        keep.append((q, p, sq, b, out))
+        arr[i] = _CorrFrame(_addr(q), _addr(p), _addr(sq), _addr(b), _addr(out))
     L = _lib.lib()
     ws = _corr_workspace(q0.device)
     vp = ctypes.c_void_p
@@ -317,9 +376,10 @@ def proxy_corr_min_records(frames, set_begin, set_size, set_out_offset, transfor
         _need_gpu(q, p, sq, b, out, qs.records, qs.sqnorm)
         assert qs.tiled and qs.n == m, "the records kernel reads aoc_split_rows_tiled records of the whole query"
         assert q.shape == (m, C) and p.shape == (n_proxy, C) and (b is None or b.numel() == n_set)
-        keep.append((q, p, sq, b))
-        arr[i] = _CorrFrameRec(q.data_ptr(), qs.records.data_ptr(), qs.sqnorm.data_ptr(), p.data_ptr(), sq.data_ptr() if sq is not None else None,
-                               b.data_ptr() if b is not None else None, out.data_ptr())
+        _span("proxy_corr_min_records: out", out, int(so.max()) + m if n_set else 0)
+        rec, rsq = qs.records, qs.sqnorm
+        keep.append((q, p, sq, b, out, rec, rsq))
+        arr[i] = _CorrFrameRec(_addr(q), _addr(rec), _addr(rsq), _addr(p), _addr(sq), _addr(b), _addr(out))
     vp = ctypes.c_void_p
     fn = _lib.lib().aoc_proxy_corr_min_records
     dev = q0.device
@@ -343,6 +403,11 @@ def proxy_corr_min_records(frames, set_begin, set_size, set_out_offset, transfor
     return launch()
 
 
+def _dense_span(m, n_obj, pixel_stride, obj_stride):
+    """Elements from the data pointer that [i * pixel_stride + o * obj_stride], i < m, o < n_obj, reaches."""
+    return (m - 1) * int(pixel_stride) + (n_obj - 1) * int(obj_stride) + 1 if m > 0 and n_obj > 0 else 0
+
+
 def dense_match_min(query_flat, pool, prep, obj_bias, out, out_pixel_stride, out_obj_stride, transform=True, float16=False):
     query_flat = _f32c(query_flat)
     pool = _f32c(pool)
@@ -353,9 +418,11 @@ def dense_match_min(query_flat, pool, prep, obj_bias, out, out_pixel_stride, out
     ws = _ws(L.aoc_dense_match_workspace_bytes(m, prep.n, n_obj), pool.device)
     if obj_bias is not None:
         obj_bias = _f32c(obj_bias)
-    n_fg = prep.counts[n_obj:n_obj + 1]
+    _span("dense_match_min: out", out, _dense_span(m, n_obj, out_pixel_stride, out_obj_stride))
+    _, wrong_bits, fg_rows, _, counts, _ = _prep_lists(prep)
+    n_fg = counts[n_obj:n_obj + 1]
     fn = L.aoc_dense_match_min_f16 if float16 else L.aoc_dense_match_min
-    _lib.check(fn(_p(query_flat), m, C, _p(pool), _p(prep.fg_rows), _p(n_fg), prep.n, _p(prep.wrong_bits),
+    _lib.check(fn(_p(query_flat), m, C, _p(pool), _p(fg_rows), _p(n_fg), prep.n, _p(wrong_bits),
                   _p(obj_bias), n_obj, _p(out), int(out_pixel_stride), int(out_obj_stride), int(bool(transform)),
                   _p(ws), ws.numel(), _stream()), "aoc_dense_match_min_f16" if float16 else "aoc_dense_match_min")
     return out
@@ -374,8 +441,11 @@ def dense_match_argmin(query_flat, pool, prep, obj_bias, out, arg, out_pixel_str
     ws = _ws(L.aoc_dense_match_argmin_workspace_bytes(m, prep.n, n_obj), pool.device)
     if obj_bias is not None:
         obj_bias = _f32c(obj_bias)
-    n_fg = prep.counts[n_obj:n_obj + 1]
-    _lib.check(L.aoc_dense_match_argmin(_p(query_flat), m, C, _p(pool), _p(prep.fg_rows), _p(n_fg), prep.n, _p(prep.wrong_bits),
+    _span("dense_match_argmin: out", out, _dense_span(m, n_obj, out_pixel_stride, out_obj_stride))
+    _span("dense_match_argmin: arg", arg, _dense_span(m, n_obj, out_pixel_stride, out_obj_stride), torch.int32)
+    _, wrong_bits, fg_rows, _, counts, _ = _prep_lists(prep)
+    n_fg = counts[n_obj:n_obj + 1]
+    _lib.check(L.aoc_dense_match_argmin(_p(query_flat), m, C, _p(pool), _p(fg_rows), _p(n_fg), prep.n, _p(wrong_bits),
                                         _p(obj_bias), n_obj, _p(out), _p(arg), int(out_pixel_stride), int(out_obj_stride), int(bool(transform)),
                                         _p(ws), ws.numel(), _stream()), "aoc_dense_match_argmin")
     return out, arg
@@ -389,10 +459,14 @@ def dense_match_backward(grad_out, T, arg, pixel_stride, obj_stride, query_flat,
     query_flat = _f32c(query_flat)
     pool = _f32c(pool)
     _need_gpu(grad_out, T, arg, query_flat, pool, grad_query, grad_pool, grad_bias)
-    assert grad_out.dtype == torch.float32 and T.dtype == torch.float32 and arg.dtype == torch.int32
     m, C = query_flat.shape
     n = pool.shape[0]
     dev = pool.device
+    # grad_out, T and arg are addressed with the caller's strides from their data pointers: they cannot be converted, only checked
+    need = _dense_span(m, n_obj, pixel_stride, obj_stride)
+    _span("dense_match_backward: grad_out", grad_out, need)
+    _span("dense_match_backward: T", T, need)
+    _span("dense_match_backward: arg", arg, need, torch.int32)
     if want_query and grad_query is None:
         grad_query = torch.empty(m, C, dtype=torch.float32, device=dev)
     if want_pool and grad_pool is None:
@@ -400,6 +474,9 @@ def dense_match_backward(grad_out, T, arg, pixel_stride, obj_stride, query_flat,
     if want_bias and grad_bias is None:
         grad_bias = torch.empty(n_obj, dtype=torch.float32, device=dev)
     gq, gp, gb = (grad_query if want_query else None), (grad_pool if want_pool else None), (grad_bias if want_bias else None)
+    for what, t, shape in (("grad_query", gq, (m, C)), ("grad_pool", gp, (n, C)), ("grad_bias", gb, (n_obj,))):
+        if t is not None:
+            _out("dense_match_backward: " + what, t, shape)
     L = _lib.lib()
     ws = _ws(L.aoc_dense_match_grad_workspace_bytes(m, n, C, n_obj), dev)
     _lib.check(L.aoc_dense_match_grad(_p(grad_out), _p(T), _p(arg), int(pixel_stride), int(obj_stride), _p(query_flat), m, C, _p(pool), n, n_obj,
@@ -413,10 +490,12 @@ def proxy_match_backward(grad_out, T, pixel_stride, obj_stride, query_flat, prox
     query_flat = _f32c(query_flat)
     proxies = _f32c(proxies)
     _need_gpu(grad_out, T, query_flat, proxies, grad_query, grad_proxies, grad_bias)
-    assert grad_out.dtype == torch.float32 and T.dtype == torch.float32
     m, C = query_flat.shape
     n_obj = proxies.shape[0]
     dev = query_flat.device
+    need = _dense_span(m, n_obj, pixel_stride, obj_stride)
+    _span("proxy_match_backward: grad_out", grad_out, need)
+    _span("proxy_match_backward: T", T, need)
     if want_query and grad_query is None:
         grad_query = torch.empty(m, C, dtype=torch.float32, device=dev)
     if want_proxies and grad_proxies is None:
@@ -424,6 +503,9 @@ def proxy_match_backward(grad_out, T, pixel_stride, obj_stride, query_flat, prox
     if want_bias and grad_bias is None:
         grad_bias = torch.empty(n_obj, dtype=torch.float32, device=dev)
     gq, gp, gb = (grad_query if want_query else None), (grad_proxies if want_proxies else None), (grad_bias if want_bias else None)
+    for what, t, shape in (("grad_query", gq, (m, C)), ("grad_proxies", gp, (n_obj, C)), ("grad_bias", gb, (n_obj,))):
+        if t is not None:
+            _out("proxy_match_backward: " + what, t, shape)
     L = _lib.lib()
     ws = _ws(L.aoc_proxy_match_grad_workspace_bytes(m, C, n_obj), dev)
     _lib.check(L.aoc_proxy_match_grad(_p(grad_out), _p(T), int(pixel_stride), int(obj_stride), _p(query_flat), m, C, _p(proxies), n_obj,
@@ -447,12 +529,14 @@ def proxy_set_match_argmin(query_flat, proxies, proxy_sqnorm, set_begin, set_siz
     proxies = _f32c(proxies)
     proxy_sqnorm = _f32c(proxy_sqnorm) if proxy_sqnorm is not None else None
     _need_gpu(query_flat, proxies, proxy_sqnorm, out, arg, set_bias)
-    assert out.dtype == torch.float32 and arg.dtype == torch.int32
     m, C = query_flat.shape
     sb, ss, so = _set_arrays(set_begin, set_size, set_out_offset)
     if set_bias is not None:
         set_bias = _f32c(set_bias)
         assert set_bias.numel() == sb.size
+    need = (m - 1) * int(out_pixel_stride) + int(so.max()) + 1 if sb.size and m else 0
+    _span("proxy_set_match_argmin: out", out, need)
+    _span("proxy_set_match_argmin: arg", arg, need, torch.int32)
     vp = ctypes.c_void_p
     _lib.check(_lib.lib().aoc_proxy_set_match_argmin(_p(query_flat), m, C, _p(proxies), _p(proxy_sqnorm), proxies.shape[0], sb.size,
                                                      sb.ctypes.data_as(vp), ss.ctypes.data_as(vp), so.ctypes.data_as(vp), _p(set_bias), _p(out), _p(arg),
@@ -468,12 +552,15 @@ def proxy_set_match_backward(grad_out, T, arg, pixel_stride, query_flat, proxies
     query_flat = _f32c(query_flat)
     proxies = _f32c(proxies)
     _need_gpu(grad_out, T, arg, query_flat, proxies, grad_query, grad_proxies, grad_bias)
-    assert grad_out.dtype == torch.float32 and T.dtype == torch.float32 and arg.dtype == torch.int32
     m, C = query_flat.shape
     dev = query_flat.device
     sb, ss, so = _set_arrays(set_begin, set_size, set_out_offset)
     si = np.ascontiguousarray(np.asarray(set_bias_index, dtype=np.int32))
     assert si.size == sb.size
+    need = (m - 1) * int(pixel_stride) + int(so.max()) + 1 if sb.size and m else 0
+    _span("proxy_set_match_backward: grad_out", grad_out, need)
+    _span("proxy_set_match_backward: T", T, need)
+    _span("proxy_set_match_backward: arg", arg, need, torch.int32)
     if want_query and grad_query is None:
         grad_query = torch.empty(m, C, dtype=torch.float32, device=dev)
     if want_proxies and grad_proxies is None:
@@ -481,6 +568,9 @@ def proxy_set_match_backward(grad_out, T, arg, pixel_stride, query_flat, proxies
     if want_bias and grad_bias is None:
         grad_bias = torch.empty(int(n_bias), dtype=torch.float32, device=dev)
     gq, gp, gb = (grad_query if want_query else None), (grad_proxies if want_proxies else None), (grad_bias if want_bias else None)
+    for what, t, shape in (("grad_query", gq, (m, C)), ("grad_proxies", gp, (proxies.shape[0], C)), ("grad_bias", gb, (int(n_bias),))):
+        if t is not None:
+            _out("proxy_set_match_backward: " + what, t, shape)
     L = _lib.lib()
     ws = _ws(L.aoc_proxy_set_match_grad_workspace_bytes(m, C, int(ss.sum())) if (want_proxies or want_bias) else 0, dev)
     vp = ctypes.c_void_p
@@ -495,10 +585,12 @@ def centroid_avg_backward(grad_proxies, fg_rows, n_fg, seg_offsets, seg_k, label
     -> grad_pool [pool_rows, C]; n_fg is the device element that holds the number of kept rows (LabelPrep.counts[n_obj:])."""
     grad_proxies = _f32c(grad_proxies)
     _need_gpu(grad_proxies, fg_rows, n_fg, seg_offsets, seg_k, labels, grad_pool)
+    fg_rows, n_fg, seg_offsets, seg_k, labels = _i32c(fg_rows), _i32c(n_fg), _i32c(seg_offsets), _i32c(seg_k), _i32c(labels)
     n_seg, two, kmax, C = grad_proxies.shape
     assert two == 2 and seg_k.numel() == n_seg and seg_offsets.numel() == n_seg + 1
     if grad_pool is None:
         grad_pool = torch.empty(int(pool_rows), C, dtype=torch.float32, device=grad_proxies.device)
+    _out("centroid_avg_backward: grad_pool", grad_pool, (int(pool_rows), C))
     L = _lib.lib()
     ws = _ws(L.aoc_centroid_avg_grad_workspace_bytes(n_seg, kmax), grad_proxies.device)
     _lib.check(L.aoc_centroid_avg_grad(_p(grad_proxies), C, _p(fg_rows), _p(n_fg), _p(seg_offsets), _p(seg_k), _p(labels), n_seg, kmax,
@@ -529,6 +621,8 @@ def split_rows(x_flat, out=None, row0=0, overflow=None, tiled=False):
     if rb == 0:
         raise _lib.AocHipError(f"split records need C % 4 == 0 and C <= 100 (got {C})")
     dev = x_flat.device
+    if overflow is not None:
+        _span("split_rows: overflow", overflow, 1, torch.int32)
     if tiled:
         assert out is None and row0 == 0
         out = SplitRows()
@@ -537,8 +631,8 @@ def split_rows(x_flat, out=None, row0=0, overflow=None, tiled=False):
         out.sqnorm = torch.empty(n, dtype=torch.float32, device=dev)
         out.overflow = overflow if overflow is not None else torch.zeros(1, dtype=torch.int32, device=dev)
         out.n = n
-        _lib.check(_lib.lib().aoc_split_rows_tiled(_p(x_flat), n, C, _p(out.records), _p(out.sqnorm), _p(out.overflow), _stream()),
-                   "aoc_split_rows_tiled")
+        rec, sq, flag = out.records, out.sqnorm, out.overflow
+        _lib.check(_lib.lib().aoc_split_rows_tiled(_p(x_flat), n, C, _p(rec), _p(sq), _p(flag), _stream()), "aoc_split_rows_tiled")
         return out
     if out is None:
         out = SplitRows()
@@ -549,8 +643,11 @@ def split_rows(x_flat, out=None, row0=0, overflow=None, tiled=False):
         row0 = 0
     rec = out.records[row0:row0 + n]
     sq = out.sqnorm[row0:row0 + n]
-    assert rec.shape[0] == n
-    _lib.check(_lib.lib().aoc_split_rows(_p(x_flat), n, C, _p(rec), _p(sq), _p(out.overflow), _stream()), "aoc_split_rows")
+    flag = out.overflow
+    _out("split_rows: out.records[row0 : row0 + n]", rec, (n, rb), torch.uint8)
+    _out("split_rows: out.sqnorm[row0 : row0 + n]", sq, (n,))
+    _span("split_rows: out.overflow", flag, 1, torch.int32)
+    _lib.check(_lib.lib().aoc_split_rows(_p(x_flat), n, C, _p(rec), _p(sq), _p(flag), _stream()), "aoc_split_rows")
     return out
 
 
@@ -583,10 +680,13 @@ def dense_match_min_split(query_flat, query_split, pool, pool_split, prep, obj_b
     if query_split.overflow.data_ptr() != flag.data_ptr():
         flag = torch.maximum(flag, query_split.overflow)
     assert not pool_split.tiled
-    _lib.check(L.aoc_dense_match_min_split(_p(query_flat), _p(query_split.records), _p(query_split.sqnorm), int(query_split.tiled), m, C, _p(pool),
-                                           _p(pool_split.records),
-                                           _p(flag), n, _p(prep.right_bits), _p(prep.wrong_bits), _p(prep.fg_rows), _p(prep.obj_rows),
-                                           _p(prep.counts), _p(prep.obj_offsets), _p(obj_bias), n_obj, _p(out), int(out_pixel_stride),
+    _span("dense_match_min_split: out", out, _dense_span(m, n_obj, out_pixel_stride, out_obj_stride))
+    right_bits, wrong_bits, fg_rows, obj_rows, counts, obj_offsets = _prep_lists(prep)
+    q_rec, q_sq, p_rec = query_split.records, query_split.sqnorm, pool_split.records
+    _lib.check(L.aoc_dense_match_min_split(_p(query_flat), _p(q_rec), _p(q_sq), int(query_split.tiled), m, C, _p(pool),
+                                           _p(p_rec),
+                                           _p(flag), n, _p(right_bits), _p(wrong_bits), _p(fg_rows), _p(obj_rows),
+                                           _p(counts), _p(obj_offsets), _p(obj_bias), n_obj, _p(out), int(out_pixel_stride),
                                            int(out_obj_stride), int(bool(transform)), _p(ws), ws.numel(), _stream()),
                "aoc_dense_match_min_split")
     return out
@@ -611,7 +711,9 @@ def dense_match(query_flat, pool, prep, obj_bias, out, out_pixel_stride, out_obj
     if precision not in ("split", "fp32", "f16"):
         raise ValueError(f"unknown dense precision {precision!r}")
     C = query_flat.shape[1]
-    if precision == "f16":            # the reference's use_float16=True arithmetic (AEM:801-803)
+    # (checked here too: the split path converts the operands first, and a refused output must be refused before anything is enqueued)
+    _span("dense_match: out", out, _dense_span(query_flat.shape[0], prep.n_obj, out_pixel_stride, out_obj_stride))
+    if precision == "f16":          # the reference's use_float16=True arithmetic (AEM:801-803)
         return dense_match_min(query_flat, pool, prep, obj_bias, out, out_pixel_stride, out_obj_stride, transform, float16=True)
     if precision == "fp32" or split_record_bytes(C) == 0 or prep.n_obj > 16:
         return dense_match_min(query_flat, pool, prep, obj_bias, out, out_pixel_stride, out_obj_stride, transform)
@@ -638,6 +740,8 @@ def resize_bilinear_planes(x, H, W, out, out_plane_stride, out_pixel_stride, inn
     _need_gpu(x, out)
     P, h, w = x.shape
     inner = P if inner_count is None else int(inner_count)
+    last = ((P - 1) // inner) * int(out_outer_stride) + min(inner - 1, P - 1) * int(out_plane_stride) if P else 0
+    _span("resize_bilinear_planes: out", out, last + (H * W - 1) * int(out_pixel_stride) + 1 if P and H * W else 0)
     _lib.check(_lib.lib().aoc_resize_bilinear_planes(_p(x), P, h, w, _p(out), H, W, inner, int(out_outer_stride), int(out_plane_stride),
                                                      int(out_pixel_stride), _stream()), "aoc_resize_bilinear_planes")
     return out
@@ -656,6 +760,7 @@ def atrous_subsample(x, rate):
 
 def resize_nearest_bits(bits, h, w, H, W):
     _need_gpu(bits)
+    bits = _i32c(bits)
     out = torch.empty(H * W, dtype=torch.int32, device=bits.device)
     _lib.check(_lib.lib().aoc_resize_nearest_bits(_p(bits), h, w, _p(out), H, W, _stream()), "aoc_resize_nearest_bits")
     return out
@@ -665,6 +770,7 @@ def local_window_match(query, prev, right_bits, radii, obj_bias, n_obj, transfor
     """query, prev [H,W,C] -> [n_obj, len(radii), H, W] (channel order [max, r_0, ...]); atrous_rate / float16 as in the reference call."""
     query, prev = _f32c(query), _f32c(prev)
     _need_gpu(query, prev, right_bits)
+    right_bits = _i32c(right_bits)
     H, W, C = query.shape
     radii = np.ascontiguousarray(np.asarray(radii, dtype=np.int32))
     out = torch.empty(n_obj, radii.size, H, W, dtype=torch.float32, device=query.device)
@@ -682,13 +788,15 @@ def local_window_match_argmin(query, prev, right_bits, radii, obj_bias, n_obj, t
     [n_obj, len(radii), H, W].  The keyword buffers, when given, are written in place."""
     query, prev = _f32c(query), _f32c(prev)
     _need_gpu(query, prev, right_bits, out, arg)
+    right_bits = _i32c(right_bits)
     H, W, C = query.shape
     radii = np.ascontiguousarray(np.asarray(radii, dtype=np.int32))
     if out is None:
         out = torch.empty(n_obj, radii.size, H, W, dtype=torch.float32, device=query.device)
     if arg is None:
         arg = torch.empty(n_obj, radii.size, H, W, dtype=torch.int32, device=query.device)
-    assert arg.dtype == torch.int32 and out.dtype == torch.float32
+    _out("local_window_match_argmin: out", out, (n_obj, radii.size, H, W))
+    _out("local_window_match_argmin: arg", arg, (n_obj, radii.size, H, W), torch.int32)
     if obj_bias is not None:
         obj_bias = _f32c(obj_bias)
     _lib.check(_lib.lib().aoc_local_window_match_argmin(_p(query), _p(prev), _p(right_bits), H, W, C, radii.ctypes.data_as(ctypes.c_void_p),
@@ -704,9 +812,11 @@ def local_match_backward(grad_out, T, arg, query, prev, window, want_query=True,
     is written for it).  The keyword buffers, when given, are written in place."""
     query, prev = _f32c(query), _f32c(prev)
     _need_gpu(grad_out, T, arg, query, prev, grad_query, grad_prev, grad_bias)
-    assert grad_out.dtype == torch.float32 and T.dtype == torch.float32 and arg.dtype == torch.int32
-    assert grad_out.is_contiguous() and T.is_contiguous() and arg.is_contiguous()
+    grad_out, T, arg = _f32c(grad_out), _f32c(T), _i32c(arg)
     n_obj, n_radii, H, W = T.shape
+    if tuple(grad_out.shape) != tuple(T.shape) or tuple(arg.shape) != tuple(T.shape) or tuple(query.shape[:2]) != (H, W) or query.shape != prev.shape:
+        raise ValueError(f"local_match_backward: grad_out {tuple(grad_out.shape)}, T {tuple(T.shape)}, arg {tuple(arg.shape)}, query {tuple(query.shape)} "
+                         f"and prev {tuple(prev.shape)} do not fit")
     C = query.shape[2]
     dev = query.device
     if want_query and grad_query is None:
@@ -716,6 +826,9 @@ def local_match_backward(grad_out, T, arg, query, prev, window, want_query=True,
     if want_bias and grad_bias is None:
         grad_bias = torch.empty(n_obj, dtype=torch.float32, device=dev)
     gq, gp, gb = (grad_query if want_query else None), (grad_prev if want_prev else None), (grad_bias if want_bias else None)
+    for what, t, shape in (("grad_query", gq, (H, W, C)), ("grad_prev", gp, (H, W, C)), ("grad_bias", gb, (n_obj,))):
+        if t is not None:
+            _out("local_match_backward: " + what, t, shape)
     L = _lib.lib()
     ws = _ws(L.aoc_local_match_grad_workspace_bytes(H, W, C, n_radii, n_obj), dev)
     _lib.check(L.aoc_local_match_grad(_p(grad_out), _p(T), _p(arg), _p(query), _p(prev), H, W, C, n_radii, n_obj, int(window),
@@ -740,9 +853,12 @@ def local_prep(cur_emb, prev_emb, prev_labels_flat, prev_pos, H2, W2, obj_bias=N
         cp[i] = (src, dst, src.numel())
     if obj_bias is not None:
         obj_bias = _f32c(obj_bias)
+    if set_bias_out is not None:
+        _out("local_prep: set_bias_out", set_bias_out, (int(n_pair_sets) + n_obj,))
+    (src_a, dst_a, n_a), (src_b, dst_b, n_b) = cp
     _lib.check(_lib.lib().aoc_local_prep(_p(cur_emb), _p(prev_emb), _p(prev_labels_flat), _p(prev_pos), h, w, C, n_obj, _p(q2), _p(p2), _p(pm2), _p(bits2),
-                                         int(H2), int(W2), _p(obj_bias), int(n_pair_sets), _p(set_bias_out), _p(cp[0][0]), _p(cp[0][1]), cp[0][2],
-                                         _p(cp[1][0]), _p(cp[1][1]), cp[1][2], _stream()), "aoc_local_prep")
+                                         int(H2), int(W2), _p(obj_bias), int(n_pair_sets), _p(set_bias_out), _p(src_a), _p(dst_a), n_a,
+                                         _p(src_b), _p(dst_b), n_b, _stream()), "aoc_local_prep")
     return q2, p2, pm2, bits2
 
 
@@ -750,13 +866,15 @@ def local_window_match_pair(query, prev_a, prev_b, right_bits, radii, obj_bias, 
     """aoc_local_window_match_pair -> [2, n_obj, len(radii), H, W]: local matching against prev_a and prev_b in one launch."""
     query, prev_a, prev_b = _f32c(query), _f32c(prev_a), _f32c(prev_b)
     _need_gpu(query, prev_a, prev_b, right_bits)
+    right_bits = _i32c(right_bits)
     H, W, C = query.shape
     radii = np.ascontiguousarray(np.asarray(radii, dtype=np.int32))
     out = torch.empty(2, n_obj, radii.size, H, W, dtype=torch.float32, device=query.device)
+    out_a, out_b = out[0], out[1]
     if obj_bias is not None:
         obj_bias = _f32c(obj_bias)
     _lib.check(_lib.lib().aoc_local_window_match_pair(_p(query), _p(prev_a), _p(prev_b), _p(right_bits), H, W, C, radii.ctypes.data_as(ctypes.c_void_p),
-                                                      int(radii.size), _p(obj_bias), n_obj, _p(out[0]), _p(out[1]), int(bool(transform)), _stream()),
+                                                      int(radii.size), _p(obj_bias), n_obj, _p(out_a), _p(out_b), int(bool(transform)), _stream()),
                "aoc_local_window_match_pair")
     return out
 
@@ -766,6 +884,12 @@ def resize_bilinear_planes_grouped(x, H, W, out, inner_count, outer_count, group
     x = _f32c(x)
     _need_gpu(x, out)
     P, h, w = x.shape
+    ic, oc = int(inner_count), int(outer_count)
+    if P and P % (ic * oc) == 0:
+        last = (P // (ic * oc) - 1) * int(group_stride) + (oc - 1) * int(outer_stride) + (ic - 1) * int(plane_stride)
+    else:
+        last = max(((p // (ic * oc)) * int(group_stride) + (p // ic % oc) * int(outer_stride) + (p % ic) * int(plane_stride) for p in range(P)), default=0)
+    _span("resize_bilinear_planes_grouped: out", out, last + (H * W - 1) * int(pixel_stride) + 1 if P and H * W else 0)
     _lib.check(_lib.lib().aoc_resize_bilinear_planes_grouped(_p(x), P, h, w, _p(out), H, W, int(inner_count), int(outer_count), int(group_stride),
                                                              int(outer_stride), int(plane_stride), int(pixel_stride), _stream()),
                "aoc_resize_bilinear_planes_grouped")
@@ -782,10 +906,15 @@ def proto_finish(feat, hw, obj_stride, ch_local, n_local, ch_local_bg, ch_global
     if ref_pos is not None:
         C = ref_pos.shape[1]
         head = torch.empty(n_obj, 4 * C, dtype=torch.float32, device=feat.device)
+        ref_pos, ref_neg, prev_pos, prev_neg = _f32c(ref_pos), _f32c(ref_neg), _f32c(prev_pos), _f32c(prev_neg)
         for t in (ref_pos, ref_neg, prev_pos, prev_neg):
-            assert t.is_contiguous() and t.shape == (n_obj, C)
+            assert t.shape == (n_obj, C)
     if prev_labels_flat is not None:
         prev_labels_flat = _f32c(prev_labels_flat)
+    # feat is read and written in place, channel by channel: the highest channel any switched-on part touches bounds what it must hold
+    top = max(max(int(ch_local), int(ch_local_bg)) + int(n_local) if int(ch_local_bg) >= 0 else 0,
+              max(int(ch_global), int(ch_global_bg)) + 1 if int(ch_global_bg) >= 0 else 0, int(ch_prev_mask) + 1, 0)
+    _span("proto_finish: feat", feat, (n_obj - 1) * int(obj_stride) + top * int(hw) if n_obj else 0)
     _lib.check(_lib.lib().aoc_proto_finish(_p(feat), n_obj, int(hw), int(obj_stride), int(ch_local), int(n_local), int(ch_local_bg), int(ch_global),
                                            int(ch_global_bg), int(ch_prev_mask), _p(prev_labels_flat), _p(ref_pos), _p(ref_neg), _p(prev_pos), _p(prev_neg),
                                            int(C), _p(head), _stream()), "aoc_proto_finish")
@@ -832,18 +961,23 @@ def cluster_chain(pool, prep, levels, init_rows, tables, sqnorms, iters=20):
     _need_gpu(pool, init_rows, *tables, *sqnorms)
     F, L, O, C = len(tables), len(levels), prep.n_obj, pool.shape[1]
     kmax = int(max(levels))
-    init_rows = init_rows.to(torch.int32).contiguous()
+    init_rows = _i32c(init_rows)
+    _, _, fg_rows, obj_rows, _, obj_offsets = _prep_lists(prep)
     if not (1 <= F <= CHAIN_MAX_FRAMES and 1 <= L <= 8 and len(sqnorms) == F and init_rows.numel() == F * L * O * kmax):
         raise _lib.AocHipError("cluster_chain: 1..8 frames, 1..8 levels, one squared-norm array per table, init_rows [F * L * O, kmax]")
     d = _ChainDesc()
     d.C, d.n_obj, d.n_frames, d.n_levels, d.kmax, d.iters = C, O, F, L, kmax, int(iters)
     for i, k in enumerate(levels):
         d.levels[i] = int(k)
-    d.pool_rows, d.rows_capacity = pool.shape[0], prep.obj_rows.numel()
-    d.pool, d.fg_rows, d.obj_rows, d.obj_offsets, d.init_rows = pool.data_ptr(), prep.fg_rows.data_ptr(), prep.obj_rows.data_ptr(), prep.obj_offsets.data_ptr(), init_rows.data_ptr()
+    d.pool_rows, d.rows_capacity = pool.shape[0], obj_rows.numel()
+    d.pool, d.fg_rows, d.obj_rows, d.obj_offsets, d.init_rows = _addr(pool), _addr(fg_rows), _addr(obj_rows), _addr(obj_offsets), _addr(init_rows)
     for f in range(F):
-        assert tables[f].is_contiguous() and tables[f].dtype == torch.float32 and tables[f].shape[0] >= L * O * 2 * kmax
-        d.tables[f], d.sqnorms[f] = tables[f].data_ptr(), sqnorms[f].data_ptr()
+        table, sqn = tables[f], sqnorms[f]
+        if table.dim() != 2 or table.shape[0] < L * O * 2 * kmax:
+            raise ValueError(f"cluster_chain: tables[{f}] {tuple(table.shape)} has fewer than {L * O * 2 * kmax} rows")
+        _out(f"cluster_chain: tables[{f}]", table, (table.shape[0], C))
+        _span(f"cluster_chain: sqnorms[{f}]", sqn, L * O * 2 * kmax)
+        d.tables[f], d.sqnorms[f] = _addr(table), _addr(sqn)
     lib = _lib.lib()
     ws = _ws(lib.aoc_cluster_chain_workspace_bytes(ctypes.byref(d)), pool.device)
     _lib.check(lib.aoc_cluster_chain_enqueue(ctypes.byref(d), _p(ws), ws.numel(), _stream()), "aoc_cluster_chain_enqueue")
@@ -853,7 +987,7 @@ def cluster_chain(pool, prep, levels, init_rows, tables, sqnorms, iters=20):
 
     def view(i, n, dtype, shape):
         return ws[off[i]:off[i] + n * 4].view(dtype).view(shape)
-    return dict(workspace=ws, keep=(pool, init_rows), centroids=view(0, S * kmax * C, torch.float32, (S, kmax, C)), labels=view(1, cap, torch.int32, (cap,)),
+    return dict(workspace=ws, keep=(pool, init_rows, fg_rows, obj_rows, obj_offsets), centroids=view(0, S * kmax * C, torch.float32, (S, kmax, C)), labels=view(1, cap, torch.int32, (cap,)),
                 cluster_counts=view(2, S * kmax, torch.int32, (S, kmax)), proxies=view(3, S * 2 * kmax * C, torch.float32, (S, 2, kmax, C)),
                 proxy_sqnorm=view(4, S * 2 * kmax, torch.float32, (S, 2, kmax)), seg_k=view(5, S, torch.int32, (S,)),
                 seg_offsets=view(6, S + 1, torch.int32, (S + 1,)))
@@ -875,17 +1009,22 @@ class GateBatch:
         self.n, self.n_obj, self.D = len(entries), int(n_obj), int(head_dim)
         self.arr = (_GateDesc * self.n)()
         self.keep, self.outs = [], []
+        self.converted = False
         for i, (kind, x, prm) in enumerate(entries):
-            assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.shape[0] == n_obj
+            _need_gpu(x, *prm[:10])
+            assert x.dtype == torch.float32 and x.is_contiguous() and x.shape[0] == n_obj
             y = torch.empty_like(x)
             ts = [_f32c(t.detach()) for t in prm[:10]]
+            # a parameter that had to be converted is read from a COPY kept here: an in-place update of the original is not seen through it
+            # (hotpath.CalibrationGates watches the parameters' versions then)
+            self.converted = self.converted or any(t.dtype != torch.float32 or not t.is_contiguous() for t in prm[:10])
             self.keep.append((x, ts))
             self.outs.append(y)
             d = self.arr[i]
             d.kind, d.channels, d.hw = int(kind), int(x.shape[1]), int(x.numel() // (x.shape[0] * x.shape[1]))
-            d.x, d.y, d.w, d.b = x.data_ptr(), y.data_ptr(), ts[0].data_ptr(), ts[1].data_ptr()
+            d.x, d.y, d.w, d.b = _addr(x), _addr(y), _addr(ts[0]), _addr(ts[1])
             if kind == 2:
-                d.phi_w, d.phi_b, d.w1, d.b1, d.w2, d.b2, d.w3, d.b3 = [t.data_ptr() for t in ts[2:10]]
+                d.phi_w, d.phi_b, d.w1, d.b1, d.w2, d.b2, d.w3, d.b3 = [_addr(t) for t in ts[2:10]]
                 d.k_rank = int(prm[10])
         L = _lib.lib()
         self.ws = torch.empty(max(16, int(L.aoc_gates_workspace_bytes(ctypes.cast(self.arr, ctypes.c_void_p), self.n, self.n_obj, self.D))),
@@ -963,8 +1102,12 @@ class FrameCall:
         R = ref_emb.shape[0]
         done = min(self.match_frames, R if pool_prefix_frames is None else int(pool_prefix_frames))
         hh, ww = (self.h + self.grate - 1) // self.grate, (self.w + self.grate - 1) // self.grate
+        assert ref_emb.dtype == torch.float32 and ref_emb.is_contiguous() and tuple(ref_emb.shape[1:]) == (self.h, self.w, self.C) and R <= self.cap, \
+            "match_pool takes the contiguous float32 pool [R <= capacity, h, w, C]"
+        _need_gpu(ref_emb)
         for r in range(done, R):
-            _lib.check(_lib.lib().aoc_atrous_subsample(_p(ref_emb[r]), self.h, self.w, self.C, self.grate, _p(self.match_emb[r]), _stream()), "aoc_atrous_subsample")
+            src, dst = ref_emb[r], self.match_emb[r]
+            _lib.check(_lib.lib().aoc_atrous_subsample(_p(src), self.h, self.w, self.C, self.grate, _p(dst), _stream()), "aoc_atrous_subsample")
         self.match_frames = R
         labs = torch.stack([atrous_subsample(ref_labels[r], self.grate) for r in range(R)])
         return self.match_emb[:R].view(R, hh, ww, self.C), labs
@@ -981,14 +1124,21 @@ class FrameCall:
         _need_gpu(ref_emb, ref_labels, prev_emb, prev_labels, cur_emb, dis_bias, table, sqn)
         for t in (ref_emb, ref_labels, prev_emb, prev_labels, cur_emb, dis_bias, table, sqn):
             assert t.dtype == torch.float32 and t.is_contiguous(), "aoc_frame_enqueue takes contiguous float32 tensors"
+        right_bits, wrong_bits, fg_rows, obj_rows, counts, obj_offsets = prep.right_bits, prep.wrong_bits, prep.fg_rows, prep.obj_rows, prep.counts, prep.obj_offsets
+        for t in (right_bits, wrong_bits, fg_rows, obj_rows, counts, obj_offsets):
+            assert t.dtype == torch.int32 and t.is_contiguous(), "aoc_frame_enqueue takes the contiguous int32 lists of ops.label_prep"
         R = ref_emb.shape[0]
         d = self.desc
         assert R <= self.cap and tuple(cur_emb.shape) == (self.h, self.w, self.C) and ref_labels.shape[-1] == self.n_obj and dis_bias.numel() == self.n_obj
-        assert table.shape[0] == d.n_adaptive + self.n_obj and prep.n == R * (self.match_hw if self.grate > 1 else self.h * self.w), \
+        hw = self.h * self.w
+        assert ref_emb.numel() == R * hw * self.C and ref_labels.numel() == R * hw * self.n_obj and prev_emb.numel() == hw * self.C \
+            and prev_labels.numel() == hw * self.n_obj and table.numel() == table.shape[0] * self.C and sqn.numel() == table.shape[0], \
+            "aoc_frame_enqueue reads whole maps and tables through bare pointers: a smaller tensor would be read past its end"
+        assert table.shape[0] == d.n_adaptive + self.n_obj and prep.n ==R * (self.match_hw if self.grate > 1 else self.h * self.w), \
             "prep = the label prep of the pool the matchings see (match_pool(...) with a global atrous rate)"
         if self.grate > 1:
             assert self.match_frames >= R, "call match_pool(ref_emb, ref_labels) first: it keeps the sub-sampled pool the matchings read"
-            d.match_hw, d.match_emb = self.match_hw, self.match_emb.data_ptr()
+            d.match_hw, d.match_emb = self.match_hw, _addr(self.match_emb)
         else:
             d.match_hw, d.match_emb = 0, None
         feat = torch.empty(self.n_obj, self.n_ch, self.h, self.w, dtype=torch.float32, device=self.device)
@@ -997,14 +1147,14 @@ class FrameCall:
         d.pool_key = int(pool_key)
         d.pool_prefix_frames = int(R if pool_prefix_frames is None else pool_prefix_frames)
         d.stream_cus = int(stream_cus)              # > 0: this call's stream runs under a CU mask of that many CUs (else: aoc_set_stream_cus)
-        d.ref_emb, d.ref_labels, d.prev_emb, d.prev_labels, d.cur_emb = ref_emb.data_ptr(), ref_labels.data_ptr(), prev_emb.data_ptr(), prev_labels.data_ptr(), cur_emb.data_ptr()
-        d.dis_bias = dis_bias.data_ptr()
-        d.right_bits, d.wrong_bits, d.fg_rows, d.obj_rows = prep.right_bits.data_ptr(), prep.wrong_bits.data_ptr(), prep.fg_rows.data_ptr(), prep.obj_rows.data_ptr()
-        d.counts, d.obj_offsets = prep.counts.data_ptr(), prep.obj_offsets.data_ptr()
-        d.proxy_table, d.proxy_sqnorm = table.data_ptr(), sqn.data_ptr()
+        d.ref_emb, d.ref_labels, d.prev_emb, d.prev_labels, d.cur_emb = _addr(ref_emb), _addr(ref_labels), _addr(prev_emb), _addr(prev_labels), _addr(cur_emb)
+        d.dis_bias = _addr(dis_bias)
+        d.right_bits, d.wrong_bits, d.fg_rows, d.obj_rows = _addr(right_bits), _addr(wrong_bits), _addr(fg_rows), _addr(obj_rows)
+        d.counts, d.obj_offsets = _addr(counts), _addr(obj_offsets)
+        d.proxy_table, d.proxy_sqnorm = _addr(table), _addr(sqn)
         d.prep_ready = prep_event.cuda_event if prep_event is not None else None
         d.proxies_ready = done_event.cuda_event if done_event is not None else None
-        d.feat, d.head = feat.data_ptr(), head.data_ptr()
+        d.feat, d.head = _addr(feat), _addr(head)
         for i in range(6):                      # measurement only: raw hipEvent_t handles (bench.py)
             d.probe[i] = probes[i] if probes is not None else None
         _lib.check(_lib.lib().aoc_frame_enqueue(ctypes.byref(d), ctypes.byref(self.state), _p(self.ws), self.ws.numel(), _stream()), "aoc_frame_enqueue")
@@ -1022,6 +1172,11 @@ def fg2bg_min(dis, n_obj, out=None, dis_obj_stride=None, out_obj_stride=None, n_
         inner = dis.numel() // (n_obj * n_ch)
         out = torch.empty((n_obj, 1) + tuple(dis.shape[2:]), dtype=torch.float32, device=dis.device)
         dis_obj_stride, out_obj_stride = n_ch * inner, inner
+    else:
+        # channel slices of larger buffers, addressed with the caller's strides: neither can be converted, both are checked
+        _need_gpu(out)
+        _span("fg2bg_min: dis", dis, (n_obj - 1) * int(dis_obj_stride) + int(n_ch) * int(inner) if n_obj else 0)
+        _span("fg2bg_min: out", out, (n_obj - 1) * int(out_obj_stride) + int(inner) if n_obj else 0)
     _lib.check(_lib.lib().aoc_fg2bg_min(_p(dis), n_obj, int(n_ch), int(inner), int(dis_obj_stride), _p(out), int(out_obj_stride), _stream()),
                "aoc_fg2bg_min")
     return out
@@ -1047,6 +1202,11 @@ def masked_mean_pool(emb, labels, epsilon, pixel_major=False, out_pos=None, out_
     L = _lib.lib()
     pos = torch.empty(n_obj, C, dtype=torch.float32, device=emb.device) if out_pos is None else out_pos
     neg = torch.empty(n_obj, C, dtype=torch.float32, device=emb.device) if out_neg is None else out_neg
+    _need_gpu(out_pos, out_neg, out_pos_sqnorm)
+    _out("masked_mean_pool: out_pos", pos, (n_obj, C))
+    _out("masked_mean_pool: out_neg", neg, (n_obj, C))
+    if out_pos_sqnorm is not None:
+        _out("masked_mean_pool: out_pos_sqnorm", out_pos_sqnorm, (n_obj,))
     ws = _ws(L.aoc_masked_mean_pool_workspace_bytes(F_, hw, n_obj, C), emb.device)
     _lib.check(L.aoc_masked_mean_pool(_p(emb), _p(labels), F_, hw, C, n_obj, int(bool(pixel_major)), float(epsilon), _p(pos), _p(neg),
                                       _p(out_pos_sqnorm), _p(ws), ws.numel(), _stream()), "aoc_masked_mean_pool")
@@ -1071,7 +1231,8 @@ def channel_scale(x, gain, out=None):
     planes = x.shape[0] * x.shape[1]
     hw = x.numel() // planes
     assert gain.numel() == planes
-    y = torch.empty_like(x) if out is None else out
+    y = torch.empty_like(x) if out is None else _out("channel_scale: out", out, x.shape)
+    _need_gpu(out)
     _lib.check(_lib.lib().aoc_channel_scale(_p(x), _p(gain), planes, hw, _p(y), _stream()), "aoc_channel_scale")
     return y
 
@@ -1084,7 +1245,8 @@ def film_scale(x, head, weight, bias, out=None):
     n_obj, channels = x.shape[0], x.shape[1]
     assert head.shape[0] == n_obj and weight.shape[0] == channels and weight.shape[1] == head.shape[1]
     hw = x.numel() // (n_obj * channels)
-    y = torch.empty_like(x) if out is None else out
+    y = torch.empty_like(x) if out is None else _out("film_scale: out", out, x.shape)
+    _need_gpu(out)
     _lib.check(_lib.lib().aoc_film_scale(_p(x), _p(head), _p(weight), _p(bias), n_obj, head.shape[1], channels, hw, _p(y), _stream()), "aoc_film_scale")
     return y
 
@@ -1183,7 +1345,7 @@ def confident_labels(probs_flat, exist_bits, join_label=None, unc_ratio=1.0):
     confident = torch.empty(n, dtype=torch.int32, device=dev)
     entropy = torch.empty(n, dtype=torch.float32, device=dev)
     if join_label is not None:
-        join_label = join_label.to(torch.int32).contiguous().reshape(-1)
+        join_label = _i32c(join_label).reshape(-1)
         assert join_label.numel() == n
     _lib.check(_lib.lib().aoc_confident_labels(_p(probs_flat), n_ch, n, int(exist_bits) & 0xFFFFFFFF, _p(join_label), float(unc_ratio), _p(labels),
                                                _p(confident), _p(entropy), _stream()), "aoc_confident_labels")
@@ -1193,7 +1355,7 @@ def confident_labels(probs_flat, exist_bits, join_label=None, unc_ratio=1.0):
 def label_onehot_nearest(label_hw, h, w, n_obj):
     """aoc_label_onehot_nearest: int label map [H, W] -> float one-hot [h, w, n_obj] at matching resolution."""
     _need_gpu(label_hw)
-    label_hw = label_hw.to(torch.int32).contiguous()
+    label_hw = _i32c(label_hw)
     H, W = label_hw.shape
     out = torch.empty(h, w, n_obj, dtype=torch.float32, device=label_hw.device)
     _lib.check(_lib.lib().aoc_label_onehot_nearest(_p(label_hw), H, W, int(h), int(w), int(n_obj), _p(out), _stream()), "aoc_label_onehot_nearest")
@@ -1241,11 +1403,11 @@ def tta_merge(logits_list, flips, H, W, exist_bits, join_label=None, unc_ratio=1
         if l.dim() != 3 or l.shape[0] != n_ch:
             raise ValueError("tta_merge: every augmentation is [n_ch, h, w] with the same n_ch")
         d.h[a], d.w[a], d.flip[a], d.exist_bits[a] = l.shape[1], l.shape[2], int(bool(flips[a])), int(bits[a]) & 0xFFFFFFFF
-        d.plane_stride[a], d.logits[a] = l.shape[1] * l.shape[2], l.data_ptr()
+        d.plane_stride[a], d.logits[a] = l.shape[1] * l.shape[2], _addr(l)
     if join_label is not None:
-        join_label = join_label.to(torch.int32).contiguous()
+        join_label = _i32c(join_label)
         assert join_label.shape == (H, W)
-        d.join_label = join_label.data_ptr()
+        d.join_label = _addr(join_label)
     out = {k: torch.empty(H, W, dtype=torch.int32, device=dev) for k in ("label", "confident", "label_flipped")}
     if d.mode == 1:
         out["confident_flipped"] = torch.empty(H, W, dtype=torch.int32, device=dev)
@@ -1253,7 +1415,7 @@ def tta_merge(logits_list, flips, H, W, exist_bits, join_label=None, unc_ratio=1
     if want_mean:
         out["mean_probs"] = torch.empty(n_ch, H, W, dtype=torch.float32, device=dev)
     for k, t in out.items():
-        setattr(d, k, t.data_ptr())
+        setattr(d, k, _addr(t))
     _lib.check(_lib.lib().aoc_tta_merge(ctypes.byref(d), _stream()), "aoc_tta_merge")
     return out
 
@@ -1269,7 +1431,7 @@ class MaskJF:
 
     def add(self, pred, gt, n_obj):
         _need_gpu(pred, gt)
-        pred, gt = pred.to(torch.int32).contiguous(), gt.to(torch.int32).contiguous()
+        pred, gt = _i32c(pred), _i32c(gt)
         H, W = pred.shape
         assert gt.shape == (H, W)
         L = _lib.lib()
@@ -1306,7 +1468,8 @@ def groupnorm_relu(x, groups, gamma, beta, eps=1e-5, residual=None, relu=True, o
     N, C = x.shape[0], x.shape[1]
     hw = x.numel() // (N * C)
     L = _lib.lib()
-    y = torch.empty_like(x) if out is None else out
+    y = torch.empty_like(x) if out is None else _out("groupnorm_relu: out", out, x.shape)
+    _need_gpu(out)
     ws = _ws(L.aoc_groupnorm_relu_workspace_bytes(N, int(groups)), x.device)
     # converted copies stay bound until the launch is enqueued: a temporary freed right after data_ptr() can be handed out again by the allocator
     g = _f32c(gamma) if gamma is not None else None
@@ -1329,7 +1492,8 @@ def groupnorm_relu_scale(x, groups, gamma, beta, eps, residual, relu, head, weig
     _need_gpu(x, gamma, beta, residual, head, weight, gate_bias)
     hw = x.numel() // (N * C)
     L = _lib.lib()
-    y = torch.empty_like(x) if out is None else out
+    y = torch.empty_like(x) if out is None else _out("groupnorm_relu_scale: out", out, x.shape)
+    _need_gpu(out)
     ws = _ws(L.aoc_groupnorm_relu_workspace_bytes(N, int(groups)), x.device)
     g = _f32c(gamma) if gamma is not None else None              # bound until the launch is enqueued (see groupnorm_relu)
     b = _f32c(beta) if beta is not None else None
@@ -1393,7 +1557,7 @@ def gct_gate_multi(plane_sums, alpha, gamma, beta, eps, l1_mode=False):
 
 
 def _ptr_array(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+    return (ctypes.c_void_p * len(tensors))(*[_addr(t) for t in tensors])
 
 
 def channel_scale_multi(x, gains, outs=None):
@@ -1465,7 +1629,7 @@ def object_logit(x, weight_bias):
     N, C, H, W = x.shape
     assert weight_bias.shape == (N, C + 1)
     out = torch.empty(N, 1, H, W, dtype=torch.float32, device=x.device)
-    base = weight_bias.data_ptr()
+    base = _addr(weight_bias)
     _lib.check(_lib.lib().aoc_object_logit(_p(x), N, C, H * W, ctypes.c_void_p(base), C + 1, ctypes.c_void_p(base + 4 * C), C + 1, _p(out), _stream()),
                "aoc_object_logit")
     return out
@@ -1498,7 +1662,8 @@ def bicubic_cat_scale(x, low=None, gain=None, size=None, out=None):
         raise _lib.AocHipError(f"aoc_bicubic_cat_scale: low must be [{N}, Cr, {H}, {W}], got {tuple(low.shape)}")
     if gain is not None and tuple(gain.shape) != (N, Ce + Cr):
         raise _lib.AocHipError(f"aoc_bicubic_cat_scale: gain must be [{N}, {Ce + Cr}], got {tuple(gain.shape)}")
-    y = torch.empty(N, Ce + Cr, H, W, dtype=torch.float32, device=x.device) if out is None else out
+    y = torch.empty(N, Ce + Cr, H, W, dtype=torch.float32, device=x.device) if out is None else _out("bicubic_cat_scale: out", out, (N, Ce + Cr, H, W))
+    _need_gpu(out)
     _lib.check(_lib.lib().aoc_bicubic_cat_scale(_p(x), _p(low), _p(gain), N, Ce, Cr, h, w, H, W, _p(y), _stream()), "aoc_bicubic_cat_scale")
     return y
 
@@ -1518,7 +1683,8 @@ def shortcut_stage(x, low, IA_head, weight, bias, want_debug=False, out=None):
     if have != want or (bias is not None and tuple(bias.shape) != (Ce + Cr,)):
         raise _lib.AocHipError(f"aoc_shortcut_stage_enqueue: low, IA_head, weight must have shapes {want} and bias [{Ce + Cr}], got {have}")
     L = _lib.lib()
-    y = torch.empty(N, Ce + Cr, H, W, dtype=torch.float32, device=x.device) if out is None else out
+    y = torch.empty(N, Ce + Cr, H, W, dtype=torch.float32, device=x.device) if out is None else _out("shortcut_stage: out", out, (N, Ce + Cr, H, W))
+    _need_gpu(out)
     pm = torch.empty(N, Ce + Cr, dtype=torch.float32, device=x.device) if want_debug else None
     gain = torch.empty(N, Ce + Cr, dtype=torch.float32, device=x.device) if want_debug else None
     ws = _ws(L.aoc_shortcut_stage_workspace_bytes(N, Ce, Cr, D), x.device)
@@ -1562,8 +1728,11 @@ def cond_codes(gap, plane_means, head, w1, b1, w2, b2, w3, b3):
     if have != want:
         raise _lib.AocHipError(f"aoc_cond_codes: plane_means, head, w1, b1, w2, b2, w3, b3 must have shapes {want}, got {have}")
     code = torch.empty(N, 2 * C + D, dtype=torch.float32, device=gap.device)
-    _lib.check(_lib.lib().aoc_cond_codes(_p(gap), _p(plane_means), _p(head), _p(_f32c(w1)), _p(_f32c(b1)), _p(_f32c(w2)), _p(_f32c(b2)), _p(_f32c(w3)),
-                                         _p(_f32c(b3)), N, C, D, _p(code), _stream()), "aoc_cond_codes")
+    # converted copies stay bound until the launch is enqueued (see groupnorm_relu): taken inline, each copy died as soon as its address was
+    # read and the next conversion was handed the same block
+    w1, b1, w2, b2, w3, b3 = _f32c(w1), _f32c(b1), _f32c(w2), _f32c(b2), _f32c(w3), _f32c(b3)
+    _lib.check(_lib.lib().aoc_cond_codes(_p(gap), _p(plane_means), _p(head), _p(w1), _p(b1), _p(w2), _p(b2), _p(w3),
+                                         _p(b3), N, C, D, _p(code), _stream()), "aoc_cond_codes")
     return code
 
 
