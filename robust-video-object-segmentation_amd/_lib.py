@@ -10,13 +10,11 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 RELEASE_SO = os.path.join(CSRC, "libaoc_hip.so")
-DEV_SO = os.path.join(CSRC, "libaoc_hip_dev.so")
-# AOC_LIB_VARIANT=dev (read HERE, in Python, never by the library): load the development build, the only one that knows the
-# developer switches of tools/README.md (timing experiments, alternative kernels).  The release library ignores the environment.
-VARIANT = os.environ.get("AOC_LIB_VARIANT", "release")
-if VARIANT not in ("release", "dev"):
-    raise ImportError(f"AOC_LIB_VARIANT={VARIANT!r}: 'release' or 'dev'")
-SO_PATH = DEV_SO if VARIANT == "dev" else RELEASE_SO
+# There is one build, and it ignores the environment.  A process that still asks for the development build must not run the other one unnoticed.
+if os.environ.get("AOC_LIB_VARIANT", "release") != "release":
+    raise ImportError(f"AOC_LIB_VARIANT={os.environ['AOC_LIB_VARIANT']!r}: the development build and its switches are gone (commit fb2052a is the last "
+                      "one that has them); unset the variable, or load a variant library of your own with AOC_LIB_FILE")
+SO_PATH = RELEASE_SO
 if os.environ.get("AOC_LIB_FILE"):          # developer override (python side): an experimental build of the library, by file name in csrc/
     SO_PATH = os.path.join(CSRC, os.environ["AOC_LIB_FILE"])
 
@@ -144,14 +142,11 @@ class AocHipError(RuntimeError):
     pass
 
 
-def build(force=False, dev=True):
-    """hipcc --offload-arch=gfx950 build of csrc/*.hip -> csrc/libaoc_hip.so (in-tree) and, with dev=True, the development
-    build csrc/libaoc_hip_dev.so (-DAOC_DEV: the same sources with the developer switches compiled in)."""
+def build(force=False):
+    """hipcc --offload-arch=gfx950 build of csrc/*.hip -> csrc/libaoc_hip.so (in-tree)."""
     if force:
         subprocess.check_call(["make", "-s", "-C", CSRC, "clean"])
     subprocess.check_call(["make", "-s", "-j4", "-C", CSRC])
-    if dev:
-        subprocess.check_call(["make", "-s", "-j4", "-C", CSRC, "DEV=1"])
     return SO_PATH
 
 

@@ -78,17 +78,8 @@ int aoc_dense_match_argmin_impl(const float *query, int64_t m, int C, const floa
 struct AocDenseProbe { hipEvent_t start, stop; };
 AocDenseProbe aoc_take_dense_probe();
 
-// Developer switches (timing experiments, alternative kernels, some of which produce WRONG results on purpose) only exist in the
-// development build (`make DEV=1` -> libaoc_hip_dev.so, -DAOC_DEV).  The release library never reads the environment: a stray
-// variable cannot change a result or a kernel choice.  tests/test_host_logic.py checks that no switch name is in the release binary.
-#include <stdlib.h>
-#ifdef AOC_DEV
-#define AOC_DEV_ENV(name) getenv(name)
-#define AOC_DEV_ENV_INT(name, dflt) (getenv(name) ? atoi(getenv(name)) : (dflt))
-#else
-#define AOC_DEV_ENV(name) (static_cast<const char *>(nullptr))      /* the switch's name is not even in the binary */
-#define AOC_DEV_ENV_INT(name, dflt) (dflt)
-#endif
+// The library never reads the environment: a stray variable cannot change a result or a kernel choice (tests/test_host_logic.py checks
+// the sources and the binary).  An experiment is a variant library built from a changed source (tools/build_variant.sh).
 
 // CUs the launching stream may use (aoc_set_stream_cus; 0 = all CUs of the device).  Defined in dense_split.hip.
 int aoc_stream_cus();

@@ -416,7 +416,7 @@ __device__ __forceinline__ void cb_tile_compute(const CbImage &L, const AocCorrT
 // wave converts its next pixel tile (VALU) or waits for LDS, its partner's MFMA chain keeps the matrix pipe busy.
 template <int NW, int NT, bool COL0>
 __global__ __launch_bounds__(NW * 64) void proxy_corr_batched_kernel(AocCorrFrames frames, int64_t m, AocCorrTiles tiles, int transform,
-                                                                      int32_t *__restrict__ gate, int dbg, int call_seq) {
+                                                                      int32_t *__restrict__ gate, int call_seq) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     // the tile tables in LDS: the staging phases index them per thread, and from the kernel-argument segment every such read is a
     // dependent global round trip (hipcc cannot use scalar loads for a per-lane index): ~30 of them per frame before
@@ -552,14 +552,14 @@ __global__ __launch_bounds__(NW * 64) void proxy_corr_batched_kernel(AocCorrFram
             // next tile: flat -> seq (its loads were issued one tile ago), then request the one after it
             fa = fb; ta = tb;
             if (fa < f_end) {
-                if (dbg != 4) convert_tile();
+                convert_tile();
                 advance(fb, tb);
-                if (fb < f_end && dbg != 2) issue_flat(fb, tb);
+                if (fb < f_end) issue_flat(fb, tb);
             }
         }
         __syncthreads();                                                      // every wave is done with this frame's image
     }
-    if (bad && dbg == 0) atomicExch(gate, call_seq);      // raised for THIS call only: no memset between calls
+    if (bad) atomicExch(gate, call_seq);      // raised for THIS call only: no memset between calls
 }
 
 // ------------------------------------------------------------------------------------------
@@ -585,7 +585,7 @@ constexpr int CR_TILE_CHUNKS = 2 * CB_SEG_STEPS * 64;                         //
 // `tiles`: the pass's tile table -- the kernel-argument copy (one pass per launch) or its copy in device memory (all passes in one launch)
 template <int NW, int NT, bool COL0>
 __device__ __forceinline__ void cr_body(uint32_t *lds, const AocCorrRecFrames &frames, int64_t m, const AocCorrTiles &tiles, int transform,
-                                        int32_t *__restrict__ gate, int dbg, int call_seq) {
+                                        int32_t *__restrict__ gate, int call_seq) {
     AocCorrTiles &ltiles = *reinterpret_cast<AocCorrTiles *>(lds);
     for (int i = threadIdx.x; i < (int)(sizeof(AocCorrTiles) / 4); i += NW * 64)
         reinterpret_cast<uint32_t *>(&ltiles)[i] = reinterpret_cast<const uint32_t *>(&tiles)[i];
@@ -664,20 +664,20 @@ __device__ __forceinline__ void cr_body(uint32_t *lds, const AocCorrRecFrames &f
             int64_t tn = ta;
             advance(fn, tn);
             cb_tile_compute<NT, COL0>(img, tiles, seq, q2, fr.out + pix, live, dump, transform, j, h, [&] {
-                if (fn < f_end && dbg != 2) issue(fn, tn);
+                if (fn < f_end) issue(fn, tn);
             });
             fa = fn; ta = tn;
         }
         __syncthreads();                                                      // every wave is done with this frame's image
     }
-    if (bad && dbg == 0) atomicExch(gate, call_seq);
+    if (bad) atomicExch(gate, call_seq);
 }
 
 template <int NW, int NT, bool COL0>
 __global__ __launch_bounds__(NW * 64, 4) void proxy_corr_records_kernel(AocCorrRecFrames frames, int64_t m, AocCorrTiles tiles, int transform,
-                                                                         int32_t *__restrict__ gate, int dbg, int call_seq) {
+                                                                         int32_t *__restrict__ gate, int call_seq) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-    cr_body<NW, NT, COL0>(lds, frames, m, tiles, transform, gate, dbg, call_seq);
+    cr_body<NW, NT, COL0>(lds, frames, m, tiles, transform, gate, call_seq);
 }
 
 // Round 5: ALL passes of a frame (a pass = up to AOC_CORR_MAX_TILES proxy tiles, what one workgroup's LDS image holds) in ONE launch:
@@ -687,21 +687,21 @@ __global__ __launch_bounds__(NW * 64, 4) void proxy_corr_records_kernel(AocCorrR
 // launches of 38 us -> one).  Every workgroup runs the specialisation of its pass (uniform switch): same code, same results as pass by pass.
 template <int NW>
 __global__ __launch_bounds__(NW * 64, 4) void proxy_corr_records_multi_kernel(AocCorrRecFrames frames, int64_t m, const AocCorrTiles *__restrict__ passes,
-                                                                               int transform, int32_t *__restrict__ gate, int dbg, int call_seq) {
+                                                                               int transform, int32_t *__restrict__ gate, int call_seq) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const AocCorrTiles &tiles = passes[blockIdx.y];
     const int key = tiles.n * 2 + (tiles.t[0].kind == 1 ? 1 : 0);
     switch (key) {
-        case 2: cr_body<NW, 1, false>(lds, frames, m, tiles, transform, gate, dbg, call_seq); break;
-        case 3: cr_body<NW, 1, true>(lds, frames, m, tiles, transform, gate, dbg, call_seq); break;
-        case 4: cr_body<NW, 2, false>(lds, frames, m, tiles, transform, gate, dbg, call_seq); break;
-        case 5: cr_body<NW, 2, true>(lds, frames, m, tiles, transform, gate, dbg, call_seq); break;
-        case 6: cr_body<NW, 3, false>(lds, frames, m, tiles, transform, gate, dbg, call_seq); break;
-        case 7: cr_body<NW, 3, true>(lds, frames, m, tiles, transform, gate, dbg, call_seq); break;
-        case 8: cr_body<NW, 4, false>(lds, frames, m, tiles, transform, gate, dbg, call_seq); break;
-        case 9: cr_body<NW, 4, true>(lds, frames, m, tiles, transform, gate, dbg, call_seq); break;
-        case 10: cr_body<NW, 5, false>(lds, frames, m, tiles, transform, gate, dbg, call_seq); break;
-        case 11: cr_body<NW, 5, true>(lds, frames, m, tiles, transform, gate, dbg, call_seq); break;
+        case 2: cr_body<NW, 1, false>(lds, frames, m, tiles, transform, gate, call_seq); break;
+        case 3: cr_body<NW, 1, true>(lds, frames, m, tiles, transform, gate, call_seq); break;
+        case 4: cr_body<NW, 2, false>(lds, frames, m, tiles, transform, gate, call_seq); break;
+        case 5: cr_body<NW, 2, true>(lds, frames, m, tiles, transform, gate, call_seq); break;
+        case 6: cr_body<NW, 3, false>(lds, frames, m, tiles, transform, gate, call_seq); break;
+        case 7: cr_body<NW, 3, true>(lds, frames, m, tiles, transform, gate, call_seq); break;
+        case 8: cr_body<NW, 4, false>(lds, frames, m, tiles, transform, gate, call_seq); break;
+        case 9: cr_body<NW, 4, true>(lds, frames, m, tiles, transform, gate, call_seq); break;
+        case 10: cr_body<NW, 5, false>(lds, frames, m, tiles, transform, gate, call_seq); break;
+        case 11: cr_body<NW, 5, true>(lds, frames, m, tiles, transform, gate, call_seq); break;
         default: break;
     }
 }
@@ -831,9 +831,8 @@ int cb_run(const aoc_corr_frame *frames_host, const AocCorrRecFrame *rec_host, i
             static const bool lds_ok = hipFuncSetAttribute(reinterpret_cast<const void *>(proxy_corr_records_multi_kernel<CR_NW>),
                                                            hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess;
             if (!lds_ok) return AOC_ERR_LAUNCH;
-            static const int dbg_m = AOC_DEV_ENV_INT("AOC_CORR_DEBUG", 0);
             hipLaunchKernelGGL((proxy_corr_records_multi_kernel<CR_NW>), dim3((unsigned)bpp, (unsigned)n_pass), dim3(CR_NW * 64), lds, st, rf, m,
-                               cb_pass_table(workspace, 0), transform, gate, dbg_m, call_seq);
+                               cb_pass_table(workspace, 0), transform, gate, call_seq);
             if (hipGetLastError() != hipSuccess) return AOC_ERR_LAUNCH;
             n_pass = 0;
             return AOC_OK;
@@ -855,7 +854,6 @@ int cb_run(const aoc_corr_frame *frames_host, const AocCorrRecFrame *rec_host, i
                 AocCorrRecFrames rf;
                 rf.n = fr.n;
                 for (int f = 0; f < fr.n; ++f) rf.f[f] = rec_host[f0 + f];
-                static const int dbg_r = AOC_DEV_ENV_INT("AOC_CORR_DEBUG", 0);
                 const bool col0_r = tab.t[0].kind == 1;
                 if (grid > 2 * (int64_t)n_cu) grid = 2 * (int64_t)n_cu;
 #define AOC_CR(N, COL)                                                                                                                  \
@@ -863,7 +861,7 @@ int cb_run(const aoc_corr_frame *frames_host, const AocCorrRecFrame *rec_host, i
         static const bool lds_ok = hipFuncSetAttribute(reinterpret_cast<const void *>(proxy_corr_records_kernel<CR_NW, N, COL>),         \
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess;             \
         if (!lds_ok) return AOC_ERR_LAUNCH;                                                                                              \
-        hipLaunchKernelGGL((proxy_corr_records_kernel<CR_NW, N, COL>), dim3((unsigned)grid), dim3(CR_NW * 64), lds, st, rf, m, tab, transform, gate, dbg_r, call_seq); \
+        hipLaunchKernelGGL((proxy_corr_records_kernel<CR_NW, N, COL>), dim3((unsigned)grid), dim3(CR_NW * 64), lds, st, rf, m, tab, transform, gate, call_seq); \
     } while (0)
                 switch (tab.n * 2 + (col0_r ? 1 : 0)) {
                     case 2: AOC_CR(1, false); break;
@@ -883,14 +881,13 @@ int cb_run(const aoc_corr_frame *frames_host, const AocCorrRecFrame *rec_host, i
                 return hipGetLastError() == hipSuccess ? AOC_OK : AOC_ERR_LAUNCH;
             }
             if (grid > n_cu) grid = n_cu;
-            static const int dbg = AOC_DEV_ENV_INT("AOC_CORR_DEBUG", 0);   // developer switch: 2 = no tile loads, 4 = no conversion (timing experiments; wrong results)
             const bool col0 = tab.t[0].kind == 1;
 #define AOC_CB(N, COL)                                                                                                                  \
     do {                                                                                                                                \
         static const bool lds_ok = hipFuncSetAttribute(reinterpret_cast<const void *>(proxy_corr_batched_kernel<NW, N, COL>),            \
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;            \
         if (!lds_ok) return AOC_ERR_LAUNCH;                                                                                              \
-        hipLaunchKernelGGL((proxy_corr_batched_kernel<NW, N, COL>), dim3((unsigned)grid), dim3(NW * 64), lds, st, fr, m, tab, transform, gate, dbg, call_seq); \
+        hipLaunchKernelGGL((proxy_corr_batched_kernel<NW, N, COL>), dim3((unsigned)grid), dim3(NW * 64), lds, st, fr, m, tab, transform, gate, call_seq); \
     } while (0)
             switch (tab.n * 2 + (col0 ? 1 : 0)) {
                 case 2: AOC_CB(1, false); break;

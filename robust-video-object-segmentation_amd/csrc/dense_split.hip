@@ -609,12 +609,7 @@ __global__ __launch_bounds__(SP_NW * 64, 1) void dense_prune_kernel(const uint4 
 // arithmetic in numpy).  Hence  seed <= exact(seed pair) <= exact(best pair) <= coarse(best pair) + eps : the best pair is still evaluated and the
 // published maximum is the same number as without seeds -- the seeds only spare pairs that could never have held it.  (~5e-4 in squared-distance units
 // on the bench's embeddings, below the kernel's own rescoring margin eps = 1.4e-3.)
-#ifndef AOC_DENSE_SEED
-#define AOC_DENSE_SEED 1
-#endif
-#ifndef AOC_DENSE_SEED_FRAMES
-#define AOC_DENSE_SEED_FRAMES 1
-#endif
+constexpr int AOC_DENSE_SEED_FRAMES = 1;
 __global__ __launch_bounds__(256) void dense_seed_kernel(const float *__restrict__ query, const float *__restrict__ q2, int64_t m, int C,
                                                           const float *__restrict__ pool, int64_t n, const uint32_t *__restrict__ right_bits, int n_obj,
                                                           const int32_t *__restrict__ gate, uint32_t *__restrict__ gbest) {
@@ -818,8 +813,7 @@ int aoc_dense_match_min_split_cached(const float *query, const void *query_rec, 
                            right_bits, wrong_bits, overflow_flag, static_cast<const uint4 *>(pool_rec), w.tile_capacity, w.tile_rows, w.tile_obj,
                            w.n_tiles, w.gate, w.pmax);
     }
-    static const bool seeds = AOC_DEV_ENV_INT("AOC_DENSE_SEED", AOC_DENSE_SEED) != 0;     // developer switch (A / B)
-    if (seeds && n >= m)
+    if (n >= m)
         hipLaunchKernelGGL(dense_seed_kernel, dim3((unsigned)((m * 8 + 255) / 256)), dim3(256), 0, st, query, query_sqnorm, m, C, pool, n, right_bits, n_obj, w.gate,
                            w.gbest);
     const dim3 grid((unsigned)((m + SP_ROWS_PER_BLOCK - 1) / SP_ROWS_PER_BLOCK), split_nsplit(m));

@@ -1211,7 +1211,7 @@ __global__ __launch_bounds__(256) void km_scan_scatter_kernel(const int32_t *__r
                                                                const int32_t *__restrict__ hist, int nb_max, int kmax, uint32_t row_bytes,
                                                                uint32_t *__restrict__ moff, int32_t *__restrict__ counts, int32_t *__restrict__ cbase,
                                                                int32_t *__restrict__ cchunk, int32_t *__restrict__ owner_cluster,
-                                                               int32_t *__restrict__ owner_local, int nch_cap, uint32_t *__restrict__ cflag) {
+                                                               int32_t *__restrict__ owner_local, int nch_cap) {
     __shared__ int32_t part[2][256];                               // [before my range | whole segment][stride group x cluster]
     __shared__ int32_t lpre[AOC_MAX_CLUSTERS], ltot[AOC_MAX_CLUSTERS], lbase[AOC_MAX_CLUSTERS];
     __shared__ int32_t loff[KSS_BLOCKS][AOC_MAX_CLUSTERS];
@@ -1304,10 +1304,6 @@ __global__ __launch_bounds__(256) void km_scan_scatter_kernel(const int32_t *__r
             }
             owner_cluster[cb + i] = oc;
             owner_local[cb + i] = ol;
-            if (cflag) {
-#pragma unroll
-                for (int g = 0; g < 8; ++g) cflag[(size_t)(cb + i) * 8 + g] = 0u;      // nothing published yet in this pass
-            }
         }
     }
     if (k <= 0) return;
@@ -1348,7 +1344,7 @@ __device__ __forceinline__ void kc_chunk_sum_body(int chunk, uint32_t *__restric
                                                   float *__restrict__ csum, int start_chunk) {
     const int oc = owner_cluster[chunk];
     if (oc < 0) return;
-    if (owner_local[chunk] < start_chunk) return;       // head chunks are summed literally (km_ordered_sum_kernel)
+    if (owner_local[chunk] < start_chunk) return;       // head chunks are summed literally (km_heads_chunk_sums_kernel)
     const int s = oc / kmax;
     const int cnt = counts[oc];
     const uint32_t *list = moff + seg_off[s] + cbase[oc];
@@ -1741,182 +1737,6 @@ __global__ __launch_bounds__(256) void km_chunk_fold_kernel(const float *__restr
                        head_state, n_chunks_grid, n_groups, xcd_aware, pred.e0 ? &pred : nullptr);
 }
 
-// P0 + P1 + P2 in one pass over the rows ("scan-fold").  Same grid and roles as km_chunk_fold_kernel, but the workgroup keeps all
-// KS_T member blocks of its chunk (its feature group's columns) in LDS and
-//   1. sums them in any order and PUBLISHES the chunk's local sums (csum + a flag per (chunk, feature group)),
-//   2. adds up the local sums of the cluster's earlier tail chunks (lanes = predecessor chunks; a chunk id is dispatched after every
-//      smaller one, so the flags it waits for belong to workgroups that are running or done) on top of the exact head sum: the
-//      any-order prefix the binade prediction needs,
-//   3. predicts the binade exactly as km_chunk_predict_kernel does and folds the staged rows in it.
-// A flag that does not arrive within the polling budget only makes the wave mark its features KC_UNSAFE: the stitch then folds that
-// chunk from its rows -- time, never exactness (and no dependence on the dispatch order for progress).
-constexpr int KC_POLL_BUDGET = 1 << 16;
-__global__ __launch_bounds__(256) void km_chunk_scanfold_kernel(const float *__restrict__ pool, int C, const int32_t *__restrict__ seg_off,
-                                                                 const int32_t *__restrict__ counts, const int32_t *__restrict__ cbase,
-                                                                 const uint32_t *__restrict__ moff, int kmax,
-                                                                 const int32_t *__restrict__ owner_cluster, const int32_t *__restrict__ owner_local,
-                                                                 const int32_t *__restrict__ cchunk, const float *__restrict__ head_state,
-                                                                 float *__restrict__ csum, uint32_t *__restrict__ cflag,
-                                                                 int8_t *__restrict__ cexp, int32_t *__restrict__ cinc0, int32_t *__restrict__ cinc1,
-                                                                 int start_chunk) {
-    __shared__ float tile[2][64 * KC_G_LD];
-    __shared__ uint32_t loffs[KS_CHUNK];
-    const int chunk = blockIdx.x, grp = blockIdx.y;
-    const int oc = owner_cluster[chunk];
-    if (oc < 0) return;
-    const int ol = owner_local[chunk];
-    if (ol < start_chunk) return;
-    const int f0 = grp * KC_FG;
-    const int s = oc / kmax;
-    const int cnt = counts[oc];
-    const uint32_t *list = moff + seg_off[s] + cbase[oc];
-    const int first = ol * KS_CHUNK;
-    const int lane = aoc_lane(), wave = threadIdx.x >> 6;
-    const int members = min(KS_CHUNK, cnt - first);
-    const int nblk = (members + 63) / 64;
-
-    for (int i = threadIdx.x; i < KS_CHUNK; i += blockDim.x) loffs[i] = (i < members) ? list[first + i] : 0u;
-    __syncthreads();
-    // staging of one member block: 64 rows x (KC_FG / 4) float4 = 320 pieces, thread t takes pieces t and t + 256 (branch-free: every
-    // lane loads from a valid address and selects afterwards).  The chunk is streamed twice through a double-buffered tile: once for
-    // the local sums, once for the folds (the second pass hits L2); keeping all KS_T blocks in LDS instead costs occupancy (45 KB).
-    const int npiece = KC_FG / 4;
-    auto issue = [&](int blk, float4 (&v)[2]) {
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            const int idx = it * 256 + threadIdx.x;
-            const int mloc = idx / npiece, piece = idx - mloc * npiece;
-            const int m = blk * 64 + mloc;
-            const bool in = idx < 64 * npiece && m < members && f0 + piece * 4 < C;
-            const float4 x = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(pool) + loffs[in ? m : 0] + (in ? (f0 + piece * 4) * 4 : 0));
-            v[it].x = in ? x.x : 0.f; v[it].y = in ? x.y : 0.f; v[it].z = in ? x.z : 0.f; v[it].w = in ? x.w : 0.f;
-        }
-    };
-    auto commit = [&](int buf, const float4 (&v)[2]) {
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            const int idx = it * 256 + threadIdx.x;
-            if (idx < 64 * npiece) {
-                const int mloc = idx / npiece, piece = idx - mloc * npiece;
-                float *d = tile[buf] + mloc * KC_G_LD + piece * 4;
-                d[0] = v[it].x; d[1] = v[it].y; d[2] = v[it].z; d[3] = v[it].w;
-            }
-        }
-    };
-    float4 v[2];
-    float local[KC_FW];
-#pragma unroll
-    for (int i = 0; i < KC_FW; ++i) local[i] = 0.0f;
-    issue(0, v);
-    commit(0, v);
-    for (int b = 0; b < nblk; ++b) {
-        if (b + 1 < nblk) issue(b + 1, v);
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < KC_FW; ++i) local[i] += tile[b & 1][lane * KC_G_LD + wave * KC_FW + i];
-        if (b + 1 < nblk) commit((b + 1) & 1, v);
-    }
-    issue(0, v);                                       // first block of the second pass: in flight under the publication and the look-back
-
-    // ---- 1. local any-order sums (wave = KC_FW features, lanes = members), published for the later chunks of the cluster
-#pragma unroll
-    for (int i = 0; i < KC_FW; ++i) {
-        local[i] = aoc_wave_sum(local[i]);
-        const int f = f0 + wave * KC_FW + i;
-        if (lane == 0 && f < C) __hip_atomic_store(csum + (size_t)chunk * C + f, local[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    // (device-scope stores go through to the memory all XCDs see; the wave waits for theirs to be acknowledged, then the flag -- no
-    // release / acquire fences: across XCDs those write back and invalidate whole L2s)
-    __builtin_amdgcn_s_waitcnt(0x0f70);                  // vmcnt(0)
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(cflag + (size_t)chunk * 8 + grp, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-
-    // ---- 2. any-order prefix: exact head sum + the local sums of the earlier tail chunks (chunk ids of a cluster are contiguous)
-    const int cc = cchunk[oc];
-    const int npred = ol - start_chunk;
-    float pre[KC_FW];
-#pragma unroll
-    for (int i = 0; i < KC_FW; ++i) {
-        const int f = f0 + wave * KC_FW + i;
-        pre[i] = (start_chunk > 0 && f < C) ? head_state[(size_t)oc * C + f] : 0.0f;
-    }
-    bool late = false;
-    for (int p0 = 0; p0 < npred; p0 += 64) {
-        const int pc = cc + start_chunk + p0 + lane;
-        const bool have = p0 + lane < npred;
-        if (have) {
-            int polls = 0;
-            while (__hip_atomic_load(cflag + (size_t)pc * 8 + grp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
-                if (++polls > KC_POLL_BUDGET) { late = true; break; }
-                __builtin_amdgcn_s_sleep(2);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < KC_FW; ++i) {
-            const int f = f0 + wave * KC_FW + i;
-            float x = 0.0f;
-            if (have && f < C) x = __hip_atomic_load(csum + (size_t)pc * C + f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            pre[i] += aoc_wave_sum(x);
-        }
-    }
-    late = __builtin_amdgcn_ballot_w64(late) != 0ull;
-
-    // ---- 3. binade prediction (the same test as km_chunk_predict_kernel) and the integer folds of the staged rows
-    KcFold k[KC_FW];
-    float inv_u[KC_FW];
-    int ebin[KC_FW];
-    bool live[KC_FW];
-    bool any_live = false;
-#pragma unroll
-    for (int i = 0; i < KC_FW; ++i) {
-        const int f = f0 + wave * KC_FW + i;
-        const float end = pre[i] + local[i];
-        int e = KC_UNSAFE;
-        if (!late && f < C && pre[i] > 1e-30f && end < 1e30f && end >= pre[i]) {
-            const int e_lo = (int)((__float_as_uint(pre[i] * 0.9995f) >> 23) & 0xff) - 127;
-            const int e_hi = (int)((__float_as_uint(end * 1.0005f) >> 23) & 0xff) - 127;
-            if (e_lo == e_hi && e_lo >= -100 && e_lo <= 100) e = e_lo;
-        }
-        live[i] = e != KC_UNSAFE;
-        if (lane == 0 && f < C && !live[i]) cexp[(size_t)chunk * C + f] = (int8_t)KC_UNSAFE;
-        inv_u[i] = __uint_as_float((uint32_t)(23 - (live[i] ? e : 0) + 127) << 23);
-        k[i].acc = 0; k[i].par0 = 0; k[i].par1 = 1; k[i].bump0 = 0; k[i].bump1 = 0; k[i].bad = 0;
-        any_live |= live[i];
-        ebin[i] = e;
-    }
-    // does any wave of the workgroup fold anything?  (uniform per workgroup: the second pass has barriers)
-    __shared__ int lany;
-    __syncthreads();                                   // every wave is done with the tile of the first pass
-    if (threadIdx.x == 0) lany = 0;
-    __syncthreads();
-    if (any_live && lane == 0) lany = 1;
-    __syncthreads();
-    if (!lany) return;
-    commit(0, v);
-    for (int b = 0; b < nblk; ++b) {
-        if (b + 1 < nblk) issue(b + 1, v);
-        __syncthreads();
-        if (any_live) {
-#pragma unroll
-            for (int i = 0; i < KC_FW; ++i)
-                if (live[i]) kc_fold_block2(tile[b & 1][lane * KC_G_LD + wave * KC_FW + i], inv_u[i], k[i]);
-        }
-        if (b + 1 < nblk) commit((b + 1) & 1, v);
-    }
-#pragma unroll
-    for (int i = 0; i < KC_FW; ++i) {
-        if (live[i]) {
-            const int f = f0 + wave * KC_FW + i;
-            const int t = ks_wave_sum(k[i].acc);
-            if (lane == 0) {
-                cexp[(size_t)chunk * C + f] = k[i].bad ? (int8_t)KC_UNSAFE : (int8_t)ebin[i];
-                cinc0[(size_t)chunk * C + f] = t + k[i].bump0;
-                cinc1[(size_t)chunk * C + f] = t + k[i].bump1;
-            }
-        }
-    }
-}
-
 // Serial stitch, one wave per (cluster, 4 features).
 // MODE 0: centroids[s,j,4q..4q+3] = ordered sum / count (empty cluster untouched, vq.py:820-823)
 // MODE 1: proxies[s,1,j,4q..] = mean of the listed rows (AEM:280), zeros when empty
@@ -2035,7 +1855,7 @@ __global__ __launch_bounds__(KS_SCAN_WAVES * 64) void km_sum_scan_kernel(const f
     }
     if (j >= seg_k[s]) return;
     const int cnt = counts[s * kmax + j];
-    if (start_chunk > 0 && cnt <= start_chunk * KS_CHUNK) return;       // finished by km_ordered_sum_kernel
+    if (start_chunk > 0 && cnt <= start_chunk * KS_CHUNK) return;       // finished by km_heads_chunk_sums_kernel
     const int lane = threadIdx.x & 63;
     float *out = (MODE == 0) ? dst + ((size_t)s * kmax + j) * C + NF * q : dst + (((size_t)s * 2 + 1) * kmax + j) * C + NF * q;
     if (cnt == 0) {
@@ -2282,12 +2102,13 @@ __global__ __launch_bounds__(KS_SCAN_WAVES * 64) void km_sum_scan_kernel(const f
 // ==========================================================================================
 // Ordered sums, literally: one workgroup per (cluster, group of 28 features), lanes = features.  The consumer wave
 // adds the member rows one after another in float32 -- the scipy sequence itself, so nothing is assumed about the
-// data (sign, range, NaN) -- while seven producer waves gather the group's 112 bytes of every member row through
-// the ordered member list into a double-buffered LDS batch: member offsets OS_DEPTH + 1 batches ahead, row pieces
-// OS_DEPTH batches ahead (all in flight across the barriers), so the chain only ever waits on LDS and costs a few
-// cycles per member.  Splitting the features over workgroups keeps the per-CU gather rate low enough for that.
+// data (sign, range, NaN) -- while producer waves gather the group's 112 bytes of every member row through the
+// ordered member list into LDS.  Splitting the features over workgroups keeps the per-CU gather rate low enough.
 // MODE 0: centroids[s,j,:] = sum / count (empty cluster untouched, vq.py:820-823)
 // MODE 1: proxies[s,1,j,:] = mean of the listed rows (AEM:280), zeros when empty
+// The first version (eight waves: seven producers with ordinary loads into a double-buffered batch of OS_BATCH rows, OS_DEPTH batches
+// ahead) left with the development build; its geometry constants stay because the heads kernel below sizes its feature groups (OS_FP)
+// and its LDS allocation (2 * OS_BATCH * OS_LD floats) by them.
 constexpr int OS_BATCH = 128;                   // rows per LDS buffer
 constexpr int OS_FP = 7;                        // 16-byte pieces (4 features each) per feature group
 constexpr int OS_LD = 32;                       // LDS row stride in floats
@@ -2298,126 +2119,9 @@ static_assert(OS_PP * OS_NPROD * 64 == OS_BATCH * OS_FP && OS_DEPTH % 2 == 0 && 
 inline int os_groups(int C) { return (C / 4 + OS_FP - 1) / OS_FP; }
 __device__ __forceinline__ int os_groups_dev(int C) { return (C / 4 + OS_FP - 1) / OS_FP; }
 
-template <int MODE>
-__device__ __forceinline__ void os_ordered_sum_body(int j, int s, int grp, float *__restrict__ os_lds, const float *__restrict__ pool, uint32_t pool_bytes, int C,
-                                                    const int32_t *__restrict__ seg_off, const int32_t *__restrict__ seg_k,
-                                                    const int32_t *__restrict__ counts, const int32_t *__restrict__ cbase,
-                                                    const uint32_t *__restrict__ moff, int kmax, float *__restrict__ dst,
-                                                    int member_cap, float *__restrict__ head_state) {
-    if (j >= seg_k[s]) return;
-    const int oc = s * kmax + j;
-    const int cnt_all = counts[oc];
-    const int f0 = grp * OS_FP * 4;
-    const int nfeat = min(OS_FP * 4, C - f0);
-    float *out = ((MODE == 0) ? dst + (size_t)oc * C : dst + (((size_t)s * 2 + 1) * kmax + j) * C) + f0;
-    if (cnt_all == 0) {
-        if (MODE == 1 && (int)threadIdx.x < nfeat) out[threadIdx.x] = 0.0f;
-        return;
-    }
-    // head mode: a cluster larger than member_cap only gets its first member_cap members summed here (the running
-    // sums go to head_state and the chunk-parallel stitch continues from there)
-    const bool head_only = member_cap > 0 && cnt_all > member_cap;
-    const int cnt = head_only ? member_cap : cnt_all;
-    const int wave = threadIdx.x >> 6, lane = aoc_lane();
-    const int nb = (cnt + OS_BATCH - 1) / OS_BATCH;
-
-    if (wave == 0) {
-        // ---- consumer: the sequential float32 sum (rows past the count are zeros: s + 0.0f == s)
-        const bool active = lane < nfeat;
-        const float *col = os_lds + (active ? lane : 0);
-        float sum = 0.0f;
-        for (int b = 0; b < nb; ++b) {
-            __syncthreads();                                   // batch b is in buffer b & 1
-            const float *t = col + (b & 1) * OS_BATCH * OS_LD;
-            float xa[16], xb[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) xa[u] = t[u * OS_LD];
-#pragma unroll
-            for (int g = 0; g < OS_BATCH / 16; g += 2) {
-#pragma unroll
-                for (int u = 0; u < 16; ++u) xb[u] = t[((g + 1) * 16 + u) * OS_LD];
-#pragma unroll
-                for (int u = 0; u < 16; ++u) sum = sum + xa[u];
-                if (g + 2 < OS_BATCH / 16) {
-#pragma unroll
-                    for (int u = 0; u < 16; ++u) xa[u] = t[((g + 2) * 16 + u) * OS_LD];
-                }
-#pragma unroll
-                for (int u = 0; u < 16; ++u) sum = sum + xb[u];
-            }
-        }
-        if (active) {
-            if (head_only) head_state[(size_t)oc * C + f0 + lane] = sum;
-            else out[lane] = sum / (float)cnt;
-        }
-        return;
-    }
-
-    // ---- producers
-    const uint32_t *list = moff + seg_off[s] + cbase[oc];
-    __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(pool), 0, pool_bytes, 0x00020000);
-    const int p = (wave - 1) * 64 + lane;
-    const int c4 = C >> 2;
-    int prow[OS_PP];
-    uint32_t pbyte[OS_PP];
-    bool pvalid[OS_PP];
-#pragma unroll
-    for (int i = 0; i < OS_PP; ++i) {
-        const int idx = i * (OS_NPROD * 64) + p;
-        prow[i] = idx / OS_FP;
-        const int piece = idx - prow[i] * OS_FP;
-        pvalid[i] = grp * OS_FP + piece < c4;
-        pbyte[i] = (uint32_t)(grp * OS_FP + piece) * 16u;
-    }
-    auto load_offs = [&](int b, uint32_t (&o)[OS_PP]) {
-#pragma unroll
-        for (int i = 0; i < OS_PP; ++i) {
-            const int m = b * OS_BATCH + prow[i];
-            const uint32_t v = list[min(m, cnt - 1)];          // branch-free (clamped index, select afterwards): all offset loads of a batch in flight together
-            o[i] = (b < nb && pvalid[i] && m < cnt) ? v + pbyte[i] : KU_INVALID_OFF;
-        }
-    };
-    auto load_rows = [&](const uint32_t (&o)[OS_PP], u32x4 (&d)[OS_PP]) {
-#pragma unroll
-        for (int i = 0; i < OS_PP; ++i) d[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o[i], 0, 0);   // out of range -> zeros
-    };
-    auto write_rows = [&](int b, const u32x4 (&d)[OS_PP]) {
-        float *base = os_lds + (b & 1) * OS_BATCH * OS_LD;
-#pragma unroll
-        for (int i = 0; i < OS_PP; ++i)
-            *reinterpret_cast<u32x4 *>(base + prow[i] * OS_LD + ((pbyte[i] >> 2) - f0)) = d[i];
-    };
-    u32x4 d[OS_DEPTH][OS_PP];
-    uint32_t o[2][OS_PP];
-    {
-        uint32_t po[OS_DEPTH + 2][OS_PP];
-#pragma unroll
-        for (int k = 0; k < OS_DEPTH + 2; ++k) load_offs(k, po[k]);
-#pragma unroll
-        for (int k = 0; k < OS_DEPTH; ++k) load_rows(po[k], d[k]);
-        write_rows(0, d[0]);
-        load_rows(po[OS_DEPTH], d[0]);                          // batch OS_DEPTH
-#pragma unroll
-        for (int i = 0; i < OS_PP; ++i) o[1][i] = po[OS_DEPTH + 1][i];
-    }
-    // at the top of iteration b: batches b + 1 .. b + DEPTH are in d[(b + 1) % DEPTH] ... (in flight), the offsets of
-    // batch b + 1 + DEPTH in o[(b + 1) & 1]
-    for (int b0 = 0; b0 < nb; b0 += OS_DEPTH) {
-#pragma unroll
-        for (int k = 0; k < OS_DEPTH; ++k) {
-            const int b = b0 + k;
-            if (b < nb) {
-                __syncthreads();                               // the consumer is done with buffer (b + 1) & 1
-                if (b + 1 < nb) write_rows(b + 1, d[(k + 1) % OS_DEPTH]);
-                load_offs(b + 2 + OS_DEPTH, o[k & 1]);
-                load_rows(o[(k + 1) & 1], d[(k + 1) % OS_DEPTH]);   // batch b + 1 + DEPTH
-            }
-        }
-    }
-}
 // ------------------------------------------------------------------------------------------
 // The same literal sums with the rows travelling by LDS-DMA (round 4): one consumer wave + two producer waves per (cluster, feature group).
-// The eight-wave version above keeps its row pieces "in flight across the barriers" only on paper: hipcc cannot count vmcnt across the
+// The eight-wave version kept its row pieces "in flight across the barriers" only on paper: hipcc cannot count vmcnt across the
 // loop's branches and drains every load in front of every barrier (s_waitcnt vmcnt(0)), so each batch of 128 members costs one full memory
 // round trip -- 6.4 ns per member, 66 us for a 10 240-member head at any depth, although the adding wave itself only needs ~3 ns (one
 // ds_read2_b32 per two members and one dependent v_add_f32 per member, at ~4 cycles per issue slot).  Here nothing the compiler sees is a
@@ -2430,7 +2134,7 @@ __device__ __forceinline__ void os_ordered_sum_body(int j, int s, int grp, float
 // A transfer costs its issuing wave 60-100 cycles (MI355X_MICROARCH.md), i.e. ~700 per step and producer against the consumer's ~770
 // (the single-wave form of this kernel, everything on the adding wave, was measured SLOWER than the old one for exactly that reason: 75
 // against 66 us).  Indices past the cluster's end are clamped to its last member (valid addresses, uniform operation counts); the last
-// batch adds +0.0f for them exactly as the zero rows of the version above did.  LDS rows are unpadded (112 B): transfer k of a producer
+// batch adds +0.0f for them exactly as the zero rows of the eight-wave version did.  LDS rows are unpadded (112 B): transfer k of a producer
 // fills slots [64 k, 64 k + 64) of its half lane-linearly, slot j = piece j % 7 of member j / 7.
 constexpr int OD_NPROD = 3;                                    // producer waves
 constexpr int OD_HALF = 64;                                    // members per producer and step
@@ -2594,15 +2298,6 @@ __device__ __forceinline__ void os_head_dma_body(int j, int s, int grp, float *_
     }
     od_wait_vm<0>();                                           // nothing may still be travelling into this workgroup's LDS when it ends
 }
-template <int MODE>
-__global__ __launch_bounds__((OS_NPROD + 1) * 64) void km_ordered_sum_kernel(const float *__restrict__ pool, uint32_t pool_bytes, int C,
-                                                                              const int32_t *__restrict__ seg_off, const int32_t *__restrict__ seg_k,
-                                                                              const int32_t *__restrict__ counts, const int32_t *__restrict__ cbase,
-                                                                              const uint32_t *__restrict__ moff, int kmax, float *__restrict__ dst,
-                                                                              int member_cap, float *__restrict__ head_state) {
-    __shared__ __attribute__((aligned(16))) float os_lds[2 * OS_BATCH * OS_LD];
-    os_ordered_sum_body<MODE>(blockIdx.x, blockIdx.y, blockIdx.z, os_lds, pool, pool_bytes, C, seg_off, seg_k, counts, cbase, moff, kmax, dst, member_cap, head_state);
-}
 // The literal heads and the any-order sums of the tail chunks only depend on the member lists, not on each other: ONE launch, the
 // first kmax * n_seg * groups workgroups take the heads (the long ones, dispatched first), the others one tail chunk each (on the
 // first four of their eight waves; the LDS allocation of the head role is reused).
@@ -2695,7 +2390,6 @@ struct KsWorkspace {
     int32_t *cchunk, *owner_cluster, *owner_local, *cinc0, *cinc1;
     float *csum, *head;
     int8_t *cexp;
-    uint32_t *cflag;          // per (chunk, feature group): local sums published (km_chunk_scanfold_kernel)
     int seg_chunks_max;       // no segment (hence no cluster) has more chunks than this
     KsPred pred;              // binades of the tail chunks as the last stitch left them (round 5)
 };
@@ -2710,7 +2404,7 @@ inline size_t ks_workspace_bytes(int64_t cap, int n_seg, int kmax) {
     return aoc_align_up((size_t)cap * 4, 256) + aoc_align_up((size_t)cap * 2, 256) + aoc_align_up((size_t)n_seg * nb * kmax * 4, 256) +
            3 * aoc_align_up((size_t)n_seg * kmax * 4, 256) + aoc_align_up(((size_t)cap + 64) * 4, 256) + 2 * aoc_align_up(nch * 4, 256) +
            3 * aoc_align_up(nch * AOC_MAX_CHANNELS / 2 * 4, 256) + aoc_align_up(nch * AOC_MAX_CHANNELS / 2, 256) +
-           aoc_align_up((size_t)n_seg * kmax * (AOC_MAX_CHANNELS / 2) * 4, 256) + aoc_align_up(nch * 8 * 4, 256) + ks_pred_bytes(n_seg, kmax);
+           aoc_align_up((size_t)n_seg * kmax * (AOC_MAX_CHANNELS / 2) * 4, 256) + ks_pred_bytes(n_seg, kmax);
 }
 inline KsWorkspace ks_carve(void *workspace, int64_t cap, int n_seg, int kmax, int64_t seg_bound = 0) {
     KsWorkspace w;
@@ -2734,7 +2428,6 @@ inline KsWorkspace ks_carve(void *workspace, int64_t cap, int n_seg, int kmax, i
     w.cinc1 = reinterpret_cast<int32_t *>(p); p += aoc_align_up(nch * AOC_MAX_CHANNELS / 2 * 4, 256);
     w.cexp = reinterpret_cast<int8_t *>(p); p += aoc_align_up(nch * AOC_MAX_CHANNELS / 2, 256);
     w.head = reinterpret_cast<float *>(p); p += aoc_align_up((size_t)n_seg * kmax * (AOC_MAX_CHANNELS / 2) * 4, 256);
-    w.cflag = reinterpret_cast<uint32_t *>(p); p += aoc_align_up(nch * 8 * 4, 256);
     {
         const size_t n = (size_t)n_seg * kmax * (AOC_MAX_CHANNELS / 2);
         w.pred.e0 = reinterpret_cast<int8_t *>(p); p += aoc_align_up(n, 256);
@@ -2750,6 +2443,9 @@ inline KsWorkspace ks_carve(void *workspace, int64_t cap, int n_seg, int kmax, i
 // crossings are rare from there on).  The variants this replaced -- literal sums only, the chunk-parallel pipeline only, heads and chunk
 // sums as two launches, the eight-wave heads without LDS-DMA, folds as a launch of their own, two or four features per stitch wave, the
 // group-major workgroup ids -- were measured and rejected (STATUS.md); commit dee710a is the last one that has them.
+// The single-pass scan-fold tail (chunk sums, look-back and folds in one launch, behind the development build's AOC_KM_FUSED=1) went the same
+// way: 3.5 against 3.9 ms per 20-iteration chain at R = 6 with one frame per chain, but 6.6 against 6.4 ms with three frames per chain and 5.7
+// against 5.6 at R = 12, because workgroups that wait for their predecessors' sums hold CU slots; commit fb2052a is the last one that has it.
 // 20 chunks = 10240 members (12 until the sum kernels' XCD-aware ids; after them, three runs each at 12 / 20 / 28 chunks: cfg2 360.3 / 359.7 / 356.0,
 // cfg3 208.5 / 212.6 / 211.1, closed evaluation loop 246 / 251 / 239).  Alone, a chain is fastest at 5-6 chunks (sweep 1 .. 8 at R = 6: 3.13, 3.03, 2.90, 2.89, 2.76, 2.78, 2.81,
 // 2.84 ms per chain; 3.12 at 16): the heads share a launch with the tail's chunk sums and are off the critical path up to about
@@ -2776,21 +2472,6 @@ inline void ks_launch_sums(hipStream_t st, const float *pool, uint32_t pool_byte
         hipLaunchKernelGGL((km_sum_scan_kernel<MODE, 1>), dim3((unsigned)((C + KS_SCAN_WAVES - 1) / KS_SCAN_WAVES) * kmax * n_seg), dim3(KS_SCAN_WAVES * 64), 0, st, pool,
                            pool_bytes, C, seg_offsets, seg_k, counts, ws.cbase, ws.moff, kmax, dst, ws.cchunk, ws.cexp, ws.cinc0, ws.cinc1, start, ws.head, n_seg, 1, pred);
     };
-#ifdef AOC_DEV
-    // developer switch AOC_KM_FUSED=1: capped literal heads by the eight-wave km_ordered_sum_kernel, then km_chunk_scanfold_kernel instead of
-    // chunk sum -> predict -> fold, and no speculative folds.  Bit-identical (all k-means tests pass in both modes); measured 3.5 vs 3.9 ms
-    // per 20-iteration chain at R = 6 with one frame per chain, but 6.6 vs 6.4 ms with three frames per chain and 5.7 vs 5.6 at R = 12:
-    // workgroups that wait for their predecessors' sums hold CU slots, so the product stays the three-kernel tail.
-    static const bool fused = AOC_DEV_ENV_INT("AOC_KM_FUSED", 0) == 1;
-    if (fused && C <= KC_FG * 8) {
-        hipLaunchKernelGGL(km_ordered_sum_kernel<MODE>, dim3(kmax, n_seg, os_groups(C)), dim3((OS_NPROD + 1) * 64), 0, st, pool, pool_bytes, C, seg_offsets,
-                           seg_k, counts, ws.cbase, ws.moff, kmax, dst, head_cap, ws.head);
-        hipLaunchKernelGGL(km_chunk_scanfold_kernel, dim3(ws.nch_cap, n_fold_groups), dim3(256), 0, st, pool, C, seg_offsets, counts, ws.cbase,
-                           ws.moff, kmax, ws.owner_cluster, ws.owner_local, ws.cchunk, ws.head, ws.csum, ws.cflag, ws.cexp, ws.cinc0, ws.cinc1, start);
-        stitch();
-        return;
-    }
-#endif
     if (spec && MODE == 0 && C <= KC_FG * 8) {
         // Where the folds run: INSIDE the heads launch (4 launches per iteration).  A heads workgroup owns 43 KB of LDS, so three fit a CU, a
         // cluster that fills its literal head keeps four of them for ~60 us, and the folds of the launch compete for the same slots; with the
@@ -2983,7 +2664,7 @@ int aoc_kmeans_segmented_rep(const float *pool, int64_t pool_rows, int C, const 
         if (fast) {
             hipLaunchKernelGGL(km_scan_scatter_kernel, sgrid, dim3(256), 0, st, rows, (const int32_t *)nullptr, seg_offsets, seg_k, n_seg, labels, ws.rank16,
                                ws.hist, ws.nb_max, kmax, (uint32_t)C * 4u, ws.moff, cluster_counts, ws.cbase, ws.cchunk, ws.owner_cluster, ws.owner_local,
-                               ws.nch_cap, ws.cflag);
+                               ws.nch_cap);
             ks_launch_sums<0>(st, pool, pool_bytes, C, seg_offsets, seg_k, cluster_counts, ws, kmax, n_seg, centroids, it > 0);
             continue;
         }
@@ -3056,7 +2737,7 @@ int aoc_build_proxies(const float *pool, int64_t pool_rows, int C, const int32_t
         const dim3 sgrid((unsigned)((seg_bound + 256 * KSS_BLOCKS - 1) / (256 * KSS_BLOCKS)), (unsigned)n_seg);
         hipLaunchKernelGGL(km_scan_scatter_kernel, sgrid, dim3(256), 0, st, (const int32_t *)nullptr, fg_rows, seg_offsets, seg_k, n_seg, labels, ws.rank16,
                            ws.hist, ws.nb_max, kmax, (uint32_t)C * 4u, ws.moff, ws.counts, ws.cbase, ws.cchunk, ws.owner_cluster, ws.owner_local,
-                           ws.nch_cap, ws.cflag);
+                           ws.nch_cap);
         ks_launch_sums<1>(st, pool, (uint32_t)((uint64_t)pool_rows * C * 4), C, seg_offsets, seg_k, ws.counts, ws, kmax, n_seg, proxies);
         hipLaunchKernelGGL(km_proxy_finish_kernel, grid, dim3(64), 0, st, centroids, seg_k, ws.counts, kmax, C, proxies, proxy_sqnorm);
         AOC_RETURN_IF_LAUNCH_FAILED();

@@ -223,26 +223,6 @@ def test_cfg4_full_size_kmeans_and_dense(aoc):
     assert tuple(feat.shape) == (O, 24, cfg.h, cfg.w) and bool(torch.isfinite(feat).all())
 
 
-def test_kmeans_bit_exact_with_the_single_pass_tail():
-    """AOC_KM_FUSED=1 (km_chunk_scanfold_kernel: chunk sums, look-back and folds in one launch) is a developer switch of the DEVELOPMENT build
-    (libaoc_hip_dev.so, AOC_LIB_VARIANT=dev), read once per process: the bit-exactness tests of the k-means pipeline are re-run in a child
-    process with that library and the switch set."""
-    import os, subprocess, sys
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    here = os.path.dirname(os.path.abspath(__file__))
-    import aoc_amd
-    if not os.path.exists(aoc_amd._lib.DEV_SO):
-        pytest.skip("development build not present (make DEV=1)")
-    env = dict(os.environ, AOC_KM_FUSED="1", AOC_LIB_VARIANT="dev")
-    # test_gpu_kmeans_paths.py: its k-means and proxy cases (adversarial tails: exact ties, crossings, moving membership), not its label lists
-    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", os.path.join(here, "test_gpu_fullsize.py"), os.path.join(here, "test_gpu_parity.py"),
-                        os.path.join(here, "test_gpu_kmeans_paths.py"),
-                        "-k", "kmeans and not single_pass and not persistent and not label_prep and not replicate and not kmeans_plan"],
-                       env=env, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-
-
 def test_kmeans_bit_exact_on_a_segment_beyond_the_inline_prediction_limit(aoc):
     """ONE object of 460 000 rows (cfg4's background at a dozen pool frames): more than 409 600 rows per segment, so iteration 0 takes the
     separate binade-prediction launch; iterations 1..19 fold their ~860 tail chunks in the binades the previous iteration recorded (round 5).

@@ -84,7 +84,7 @@ all_chain.sort()
 all_prox.sort()
 print(f"k-means chain {CFG} R={R} F={F}: median {all_chain[len(all_chain) // 2]:.3f} ms (min {all_chain[0]:.3f}, max {all_chain[-1]:.3f}) per chain, "
       f"proxy construction median {all_prox[len(all_prox) // 2]:.3f} ms", flush=True)
-# a library built with -DAOC_KS_STATS (tools/build_variant.sh kstat labels_kmeans.hip "-DAOC_KS_STATS -DAOC_DEV"; AOC_LIB_FILE=libaoc_hip_kstat.so) counts what
+# a library built with -DAOC_KS_STATS (tools/build_variant.sh kstat labels_kmeans.hip "-DAOC_KS_STATS"; AOC_LIB_FILE=libaoc_hip_kstat.so) counts what
 # the stitch did with the tail chunks' summaries over everything above
 try:
     import ctypes
