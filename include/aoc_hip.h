@@ -581,6 +581,50 @@ int aoc_centroid_avg_grad(const float *grad_proxies, int C, const int32_t *fg_ro
                           int n_seg, int kmax, int64_t rows_capacity, float *grad_pool, int64_t pool_rows,
                           void *workspace, size_t workspace_bytes, aoc_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Training-time front end of the proto-mask tensor (csrc/frontend_grad.hip; aoc_amd.frontend_train): streaming kernels, lanes along hw.
+ * A thread moves 16 bytes (four consecutive pixels) when every row it touches starts on a 16-byte boundary -- hw (inner) and every stride
+ * a multiple of 4 floats, every pointer 16-byte aligned; otherwise the same kernel runs with one pixel per thread and 4-byte accesses,
+ * still coalesced.  The choice depends on shapes and pointers alone and changes no bit.  No float atomics; every sum in ascending object
+ * order; every argmin takes the lowest (object, channel) among equal minima, the order of the reference's concatenation (AEM:13-19).
+ *
+ * The backward of aoc_masked_mean_pool for one frame (ATT:134-153; ATT:81-87 / 136-142 are the forward lines it differentiates):
+ *   Np_o = sum_p l[o,p],  Nn_o = sum_p (1 - l[o,p])       (computed here: per object, thread t of 256 adds pixels t, t + 256, ... in
+ *                                                          ascending order, then a binary tree over the 256 partial sums)
+ *   grad_emb[c,p] = sum_o ( grad_pos[o,c] / (Np_o + eps) * l[o,p]  +  grad_neg[o,c] / (Nn_o + eps) * (1 - l[o,p]) )
+ * added in ascending o, an object's positive term before its negative one.  labels [n_obj, hw], or [hw, n_obj] when labels_pixel_major
+ * (read with 4-byte accesses at a stride of n_obj floats between lanes then: not coalesced, the one operand here that is not); grad_pos, grad_neg [n_obj, C] (grad_neg may be NULL: its term is left out); grad_emb [C, hw], the
+ * planes of the caller's [C, h, w] embedding -- the channel-last copy the forward reads is not differentiated through.  Labels get no
+ * gradient.  n_obj <= 32.  workspace: the 2 n_obj counts. */
+size_t aoc_masked_mean_pool_grad_workspace_bytes(int n_obj);
+int aoc_masked_mean_pool_grad(const float *grad_pos, const float *grad_neg, const float *labels, int64_t hw, int C, int n_obj, int labels_pixel_major,
+                              float epsilon, float *grad_emb, void *workspace, size_t workspace_bytes, aoc_stream_t stream);
+
+/* The backward of aoc_fg2bg_min (AEM:9-23; torch.min of AEM:20 sends the gradient to one entry): per x the lowest entry (o1, c1) of
+ * dis [n_obj, n_ch, inner] and the lowest entry (o2, c2) among the objects other than o1 are recomputed from the saved dis (no index
+ * tensor); winner(o, x) = (o1, c1) for o != o1 and (o2, c2) for o = o1, so
+ *   grad_dis[o1, c1, x] = sum over o != o1, ascending from 0.0f, of grad_out[o, x];   grad_dis[o2, c2, x] = grad_out[o1, x];   0 elsewhere.
+ * dis / grad_dis / grad_out are addressed with their object strides as in the forward; all n_obj * n_ch * inner elements of grad_dis are
+ * written.  n_obj >= 2 (one object is the identity, AEM:10-11). */
+int aoc_fg2bg_grad(const float *grad_out, int64_t grad_out_obj_stride, const float *dis, int n_obj, int n_ch, int64_t inner, int64_t dis_obj_stride,
+                   float *grad_dis, int64_t grad_dis_obj_stride, aoc_stream_t stream);
+
+/* The training form of aoc_proto_finish plus the concatenation of aocnet.py:341-358, one launch each way.  The five matching outputs as
+ * planes: global_fg, proxy_fg [n_obj, 1, hw]; cluster_fg [n_obj, n_cluster, hw]; local_fg, local_proxy_fg [n_obj, n_local, hw];
+ * prev_label [n_obj, hw] (aocnet.py:155).  feat [n_obj, n_ch, hw], channels in the order of aocnet.py:355-358:
+ *   global | cluster | proxy | local | local proxy | previous mask | (background != 0: local background [n_local] | global background)
+ * background channel = per channel the min over the OTHER objects (aocnet.py:349-353; the values of aoc_fg2bg_min bit for bit); one
+ * object copies its foreground (AEM:10-11).  n_ch = aoc_proto_aggregate_channels.  Each source is read once.
+ * The backward reads grad_feat and the saved feat (the foreground channels in it name the winners: lowest object among equal minima):
+ *   grad_fg[o'] = grad_feat_fg[o'], then + grad_feat_bg[o] for every o with winner(o) = o', in ascending o;
+ * one object adds the two.  The mask channel gets none.  A NULL gradient pointer skips that source. */
+int aoc_proto_aggregate_channels(int n_cluster, int n_local, int background);
+int aoc_proto_aggregate(const float *global_fg, const float *cluster_fg, const float *proxy_fg, const float *local_fg, const float *local_proxy_fg,
+                        const float *prev_label, int n_obj, int64_t hw, int n_cluster, int n_local, int background, float *feat, aoc_stream_t stream);
+int aoc_proto_aggregate_grad(const float *grad_feat, const float *feat, int n_obj, int64_t hw, int n_cluster, int n_local, int background,
+                             float *grad_global, float *grad_cluster, float *grad_proxy, float *grad_local, float *grad_local_proxy,
+                             aoc_stream_t stream);
+
 /* ---- round 4: fused per-frame launches (each replaces several of the calls above and computes the same expressions term by term, so
  * the outputs equal theirs bit for bit; hotpath.proto_mask_features and aoc_frame_enqueue both use them) ---------------------------- */
 

@@ -131,6 +131,12 @@ SIGNATURES = {
     "aoc_proxy_set_match_grad": (_i, [_vp, _vp, _vp, _i64, _vp, _i64, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "aoc_centroid_avg_grad_workspace_bytes": (_sz, [_i, _i]),
     "aoc_centroid_avg_grad": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _i64, _vp, _sz, _vp]),
+    "aoc_masked_mean_pool_grad_workspace_bytes": (_sz, [_i]),
+    "aoc_masked_mean_pool_grad": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _f, _vp, _vp, _sz, _vp]),
+    "aoc_fg2bg_grad": (_i, [_vp, _i64, _vp, _i, _i, _i64, _i64, _vp, _i64, _vp]),
+    "aoc_proto_aggregate_channels": (_i, [_i, _i, _i]),
+    "aoc_proto_aggregate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _vp, _vp]),
+    "aoc_proto_aggregate_grad": (_i, [_vp, _vp, _i, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 STATUS = {0: "AOC_OK", -1: "AOC_ERR_INVALID_ARG", -2: "AOC_ERR_WORKSPACE", -3: "AOC_ERR_LAUNCH", -4: "AOC_ERR_UNSUPPORTED"}
