@@ -625,6 +625,70 @@ int aoc_proto_aggregate_grad(const float *grad_feat, const float *feat, int n_ob
                              float *grad_global, float *grad_cluster, float *grad_proxy, float *grad_local, float *grad_local_proxy,
                              aoc_stream_t stream);
 
+/*
+ * Training-time calibration gates (csrc/gate_grad.hip; aoc_amd.gates_train): the backward of IA_gate, GCT and the conditioning block.
+ * fp32.  No float atomics; every sum runs in an order fixed by the shapes and the pointers' 16-byte alignment, so the same buffers give
+ * the same bits.  The three streaming entries (channel_scale_grad, gct_scale_grad, cond_scale_grad) cut a plane by the alignment of the
+ * plane they write (of grad_y for the plane dot): up to 3 scalar floats in front, 16 bytes per lane for the body, up to 3 scalars behind;
+ * sources are loaded 16 bytes per lane at 4-byte alignment, so source planes may sit at other misalignments.  Every pointer marked
+ * optional may be NULL and its work is skipped.  N, n_obj <= AOC_MAX_OBJECTS.  The three streaming entries take up to 2^31 - 1 planes
+ * (one workgroup row per plane on the grid's x axis); aoc_film_gain_grad wants n_obj + channels <= 65 535 and aoc_cond_codes_grad
+ * N + 2 C + D <= 65 535 (their rows ride on the grid's y axis); beyond that they return AOC_ERR_UNSUPPORTED and enqueue nothing.
+ *
+ * The backward of y[p,:] = gain[p] * x[p,:] (ATT:16 `a * x`, gct.py:36 `x * gate`, CLB:84), one pass over the two inputs:
+ *   grad_x[p,i] = gain[p] * grad_y[p,i]               (optional; needs gain)
+ *   dgain[p]    = sum_i grad_y[p,i] * x[p,i]           (optional; needs x)
+ * One workgroup of T threads per plane (T = 256 up to 2 048 float4 per plane, else 1 024).  Order of the sum: thread t adds its front
+ * scalar, the float4 t, t + T, ... (x, y, z, w in turn) and its back scalar, every product rounded first; the 64 lanes of a wave by xor
+ * butterfly (32, 16, ... 1); the waves in ascending order from 0.0f.  With grad_x == NULL this is the plane dot of the other backwards. */
+int aoc_channel_scale_grad(const float *grad_y, const float *x, const float *gain, int64_t planes, int64_t hw, float *grad_x, float *dgain,
+                           aoc_stream_t stream);
+
+/* Through gain = 1 + tanh(head W^T + b) (ATT:12-15; the last linear of CLB:81-82):  da[o,c] = dgain[o,c] * (1 - t^2), t = gain[o,c] - 1;
+ *   grad_head[o,d]   = sum_c da[o,c] * weight[c,d]     ascending c from 0.0f
+ *   grad_weight[c,d] = sum_o da[o,c] * head[o,d]       ascending o from 0.0f
+ *   grad_bias[c]     = sum_o da[o,c]                   ascending o from 0.0f
+ * each optional.  dgain, gain [n_obj, channels]; head [n_obj, head_dim]; weight [channels, head_dim]. */
+int aoc_film_gain_grad(const float *dgain, const float *gain, const float *head, const float *weight, int n_obj, int head_dim, int channels,
+                       float *grad_head, float *grad_weight, float *grad_bias, aoc_stream_t stream);
+
+/* The backward of aoc_gct_gate (gct.py:19-34): dgate, gate, plane_sums [N, C]; du = dgate * (1 - t^2), t = gate - 1.
+ *   l2 (gct.py:20-21): e_c = sqrt(S_c + eps) alpha_c, M = mean_c e_c^2, r = sqrt(M + eps), dM = -1/2 (sum_c du_c e_c gamma_c) / (r (M + eps)),
+ *        de_c = du_c gamma_c / r + 2 e_c dM / C,      dsum[n,c] = de_c alpha_c / (2 sqrt(S_c + eps)),  grad_alpha_c += de_c sqrt(S_c + eps)
+ *   l1 (gct.py:28-29): e_c = S_c alpha_c, M = mean_c |e_c|, r = M + eps, dM = -(sum_c du_c e_c gamma_c) / r^2,
+ *        de_c = du_c gamma_c / r + sign(e_c) dM / C,  dsum[n,c] = de_c alpha_c,                        grad_alpha_c += de_c S_c
+ *        (sign(0) = 0, torch's choice for d|e|)
+ *   both: grad_gamma_c += du_c e_c / r,  grad_beta_c += du_c.
+ * The sums over c: thread t of 256 adds c = t, t + 256, ..., then the wave butterfly, then the wave sums as (0 + 1) + (2 + 3).  The sums
+ * over n: ascending n from 0.0f.  `beta` is not read (the saved gate carries it).  dsum and the three gradients [C] are optional. */
+int aoc_gct_gate_grad(const float *dgate, const float *gate, const float *plane_sums, const float *alpha, const float *gamma, const float *beta, int N,
+                      int C, float eps, int l1_mode, float *dsum, float *grad_alpha, float *grad_gamma, float *grad_beta, aoc_stream_t stream);
+
+/* GCT's apply pass (gct.py:19-36): grad_x[p,i] = grad_y[p,i] * gate[p] + dsum[p] * f'(x[p,i]), f' = 1 / 2x / sign(x) for aoc_plane_reduce's
+ * mode 0 / 1 / 2.  No sum. */
+int aoc_gct_scale_grad(const float *grad_y, const float *x, const float *gate, const float *dsum, int mode, int64_t planes, int64_t hw, float *grad_x,
+                       aoc_stream_t stream);
+
+/* The backward of aoc_cond_codes (CLB:68-80).  dcode [N, 2C + D] = (dcode_1 | dcode_2 | dcode_3); gap, plane_means [N, C]; head [N, D];
+ * w1, w2 [C, C]; w3 [D, D].  Each output optional:
+ *   dgap[n,j]      = sum_i dcode_1[n,i] w1[i,j]                       grad_head[n,j] = sum_i dcode_3[n,i] w3[i,j]          ascending i
+ *   dpx[n,j]       = (sum_m dd[m,j]) - dd[n,j],  dd[m,j] = sum_i dcode_2[m,i] w2[i,j]     (CLB:69 backwards; ascending m, ascending i)
+ *   grad_w1[i,j]   = sum_n dcode_1[n,i] gap[n,j]     grad_w3[i,j] = sum_n dcode_3[n,i] head[n,j]     grad_b*[i] = sum_n dcode_*[n,i]
+ *   grad_w2[i,j]   = sum_n dcode_2[n,i] delta[n,j],  delta[n,j] = (sum_m plane_means[m,j]) - plane_means[n,j] as aoc_cond_codes forms it
+ * all sums ascending from 0.0f.  C may be 0: the third code alone is the backward of one square aoc_linear (conditioning_layer's
+ * mlp_layer, CLB:46). */
+int aoc_cond_codes_grad(const float *dcode, const float *gap, const float *plane_means, const float *head, const float *w1, const float *w2,
+                        const float *w3, int N, int C, int D, float *dgap, float *dpx, float *grad_head, float *grad_w1, float *grad_b1, float *grad_w2,
+                        float *grad_b2, float *grad_w3, float *grad_b3, aoc_stream_t stream);
+
+/* The conditioning block's apply pass (CLB:68, 72, 84 with CLB:36-43):
+ *   grad_x[n,c,p] = (grad_y[n,c,p] * gain[n,c] + (scores[n,p] > threshold[n] ? dgap[n,c] / hw : 0)) + dpx[n,c] / hw
+ * The mask is recomputed from the scores and threshold aoc_cond_gate_pool_ex emitted, with the same strict `>`; no mask tensor exists.
+ * dgap, dpx optional (their term is 0.0f); grad_y optional together with gain (the first term is dropped: conditioning_layer's own
+ * backward, CLB:36-43, with dpx == NULL).  phi_layer gets no gradient: CLB:36 compares. */
+int aoc_cond_scale_grad(const float *grad_y, const float *gain, const float *scores, const float *threshold, const float *dgap, const float *dpx, int N,
+                        int C, int64_t hw, float *grad_x, aoc_stream_t stream);
+
 /* ---- round 4: fused per-frame launches (each replaces several of the calls above and computes the same expressions term by term, so
  * the outputs equal theirs bit for bit; hotpath.proto_mask_features and aoc_frame_enqueue both use them) ---------------------------- */
 

@@ -137,6 +137,12 @@ SIGNATURES = {
     "aoc_proto_aggregate_channels": (_i, [_i, _i, _i]),
     "aoc_proto_aggregate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _vp, _vp]),
     "aoc_proto_aggregate_grad": (_i, [_vp, _vp, _i, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "aoc_channel_scale_grad": (_i, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "aoc_film_gain_grad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "aoc_gct_gate_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp]),
+    "aoc_gct_scale_grad": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i64, _vp, _vp]),
+    "aoc_cond_codes_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "aoc_cond_scale_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _vp]),
 }
 
 STATUS = {0: "AOC_OK", -1: "AOC_ERR_INVALID_ARG", -2: "AOC_ERR_WORKSPACE", -3: "AOC_ERR_LAUNCH", -4: "AOC_ERR_UNSUPPORTED"}

@@ -40,7 +40,9 @@ _TRAINABLE = {"global_matching_for_eval": "matching_train.global_matching", "glo
               "local_matching": "local_train.local_matching", "local_matching_proxy": "local_train.local_matching_proxy",
               "global_matching_for_eval_cluster": "cluster_train.global_matching_cluster2",
               "foreground2background": "frontend_train.foreground2background",
-              "calculate_attention_head_for_eval_p_m": "frontend_train.calculate_attention_head_p_m"}
+              "calculate_attention_head_for_eval_p_m": "frontend_train.calculate_attention_head_p_m",
+              "IA_gate": "gates_train.IA_gate", "GCT": "gates_train.GCT", "conditioning_layer": "gates_train.conditioning_layer",
+              "conditioning_block": "gates_train.conditioning_block"}
 
 
 def inference_only(what, *tensors):
@@ -48,8 +50,8 @@ def inference_only(what, *tensors):
     training-time names (IA_gate, conditioning_block, GCT, global_matching, ...) into a training run would therefore train
     nothing, silently.  Raise instead when autograd is recording and an input or parameter wants a gradient.  The functions that do
     have a backward live in aoc_amd.matching_train (global_matching, global_matching_proxy), aoc_amd.local_train (local_matching,
-    local_matching_proxy), aoc_amd.cluster_train (global_matching_cluster2) and aoc_amd.frontend_train (foreground2background, the attention
-    heads, the aggregation); the error text says so for them."""
+    local_matching_proxy), aoc_amd.cluster_train (global_matching_cluster2), aoc_amd.frontend_train (foreground2background, the attention
+    heads, the aggregation) and aoc_amd.gates_train (IA_gate, GCT, conditioning_layer, conditioning_block); the error text says so for them."""
     if torch.is_grad_enabled():
         for t in tensors:
             if torch.is_tensor(t) and t.requires_grad:
