@@ -689,6 +689,49 @@ int aoc_cond_codes_grad(const float *dcode, const float *gap, const float *plane
 int aoc_cond_scale_grad(const float *grad_y, const float *gain, const float *scores, const float *threshold, const float *dgap, const float *dpx, int N,
                         int C, int64_t hw, float *grad_x, aoc_stream_t stream);
 
+/*
+ * Training-time decoder forms (csrc/norm_grad.hip; aoc_amd.decoder_train): the backward of the Bottleneck's normalisations and of the
+ * modulators' concatenation gate.  fp32, no float atomics, every sum in an order fixed by the shapes and the pointers' 16-byte alignment;
+ * every pointer marked optional may be NULL and its work is skipped; every argument is validated before the first launch, and a call that
+ * is rejected enqueues nothing.  N, n_obj <= AOC_MAX_OBJECTS; the planes ride on the grid's x axis, so N * C (n_obj * (Cx + Cm)) may reach
+ * 2^31 - 1 -- the forward's 65 535 limit is not inherited; beyond that AOC_ERR_UNSUPPORTED.
+ *
+ * The backward of aoc_groupnorm_relu and of aoc_groupnorm_relu_scale (gct.py:71-72, 75-76, 79-90 `out = self.bn3(out); out += residual;
+ * out = self.relu(out)`, and ATT:16 `a * x` of the gate behind it, decoding_module.py:196,198 / :206,208):
+ *   y = [gain[n,c] *] [relu]( z ),   z = xhat * gamma[c] + beta[c] [+ residual],   xhat = (x - mean) * rstd.
+ * grad_y, x, residual (optional) [N, C, hw]; stats [N * groups][2] = (mean, rstd) as the forward left them at the start of its workspace;
+ * gamma, beta [C] or NULL (1, 0); gain [N, C] or NULL (the ungated form).  With a = relu(z) (z when relu == 0), da = gain * grad_y (grad_y
+ * without gain), dz = da where z > 0 else 0 (da when relu == 0; the strict `>` of torch's ReLU backward), M = (C / groups) * hw:
+ *   A[n,c] = sum_p dz        B[n,c] = sum_p dz * xhat        dgain[n,c] = sum_p grad_y * a                          (plane sums)
+ *   s1[n,g] = sum_{c in g} gamma_c * A[n,c]        s2[n,g] = sum_{c in g} gamma_c * B[n,c]                           (ascending c from 0.0f)
+ *   grad_gamma[c] = sum_n B[n,c]                   grad_beta[c] = sum_n A[n,c]                                      (ascending n from 0.0f)
+ *   grad_residual = dz                             grad_x = rstd * ((gamma_c * dz - s1 / M) - xhat * (s2 / M)),     M as (float)M
+ * grad_x, grad_residual [N, C, hw], grad_gamma, grad_beta [C] and dgain [N, C] are each optional, and each has the same bits whether it is
+ * asked for alone or with the others.  z is recomputed with the forward's own float expression (x * a + b, a = rstd * gamma_c,
+ * b = beta_c - mean * a, then + residual), so the mask is the forward's.  Plane sums: one workgroup of T threads per plane (T = 256 up to
+ * 2 048 float4 per plane, else 1 024), the plane cut by grad_y's alignment, in aoc_channel_scale_grad's order: thread t adds its front scalar,
+ * the float4 t, t + T, ... (x, y, z, w in turn) and its back scalar, every product rounded first; the 64 lanes of a wave by xor butterfly
+ * (32, 16, ... 1); the waves in ascending order from 0.0f.  Three launches (plane pass, the small sums, apply pass): grad_y, x and the residual
+ * are read at most twice, every gradient is written once, nothing of activation size is stored in between.  The apply pass cuts a plane by
+ * the alignment of grad_x's plane (grad_residual's when grad_x == NULL).  The workspace holds A, B [N, C] and (s1, s2) / M [N * groups][2]; it
+ * is needed when grad_x, grad_gamma or grad_beta is asked for (else it may be NULL): AOC_ERR_WORKSPACE when it is short. */
+size_t aoc_groupnorm_relu_grad_workspace_bytes(int N, int C, int groups);
+int aoc_groupnorm_relu_grad(const float *grad_y, const float *x, const float *residual, const float *stats, const float *gamma, const float *beta,
+                            const float *gain, int N, int C, int64_t hw, int groups, int relu, float *grad_x, float *grad_residual, float *grad_gamma,
+                            float *grad_beta, float *dgain, void *workspace, size_t workspace_bytes, aoc_stream_t stream);
+
+/* The backward of aoc_cat_film_scale (decoding_module.py:193-194 / :203-204: `torch.cat([x, x_memory], dim=1)` and the IA_gate's `a * x`,
+ * ATT:16) in one pass; the concatenation is never materialised.  grad_y [n_obj, Cx + Cm, hw]; x [n_obj, Cx, hw]; mem [n_obj, Cm, hw] (may
+ * alias x; NULL with Cm = 0); gain [n_obj, Cx + Cm].  Each output optional:
+ *   grad_x[o, c]   = gain[o, c] * grad_y[o, c]              (c < Cx; needs gain)
+ *   grad_mem[o, c] = gain[o, Cx + c] * grad_y[o, Cx + c]    (needs gain and Cm >= 1; the modulators' memory is detached and asks for none)
+ *   dgain[o, c]    = sum_p grad_y[o, c, p] * cat(x, mem)[o, c, p]            (needs x, and mem when Cm >= 1)
+ * One workgroup per plane of grad_y, the plane cut by GRAD_Y's alignment whatever is written (so dgain's bits do not depend on the other
+ * outputs), the sum in aoc_channel_scale_grad's order (above); gradient planes at another misalignment are stored 16 bytes per lane at 4-byte
+ * alignment.  dgain then goes through aoc_film_gain_grad to grad_head, grad_weight and grad_bias. */
+int aoc_cat_film_scale_grad(const float *grad_y, const float *x, const float *mem, const float *gain, int n_obj, int Cx, int Cm, int64_t hw, float *grad_x,
+                            float *grad_mem, float *dgain, aoc_stream_t stream);
+
 /* ---- round 4: fused per-frame launches (each replaces several of the calls above and computes the same expressions term by term, so
  * the outputs equal theirs bit for bit; hotpath.proto_mask_features and aoc_frame_enqueue both use them) ---------------------------- */
 
@@ -863,7 +906,9 @@ int aoc_background_merge(const float *fg, const float *bg, int N, int64_t hw, fl
 /* GroupNorm (+ residual) + ReLU of the decoder's Bottleneck (networks/layers/gct.py:69-90: bn1/bn2 followed by relu, bn3 followed by
  * `out += residual; relu`): y = [relu]( GroupNorm_groups(x) * gamma + beta [+ residual] ), x [N, C, hw], biased variance over each
  * group's channels x hw as torch.nn.GroupNorm.  Two streams over x (statistics, apply) and one write instead of the separate
- * normalisation / add / ReLU passes.  gamma, beta [C] or NULL; residual [N, C, hw] or NULL; y may alias x. */
+ * normalisation / add / ReLU passes.  gamma, beta [C] or NULL; residual [N, C, hw] or NULL; y may alias x.
+ * The workspace starts with the statistics, float [N * groups][2] = (mean, rstd) of each (sample, group), rounded to float once each:
+ * aoc_groupnorm_relu_grad reads them from there (the training twin keeps the workspace instead of recomputing them). */
 size_t aoc_groupnorm_relu_workspace_bytes(int N, int groups);
 int aoc_groupnorm_relu(const float *x, int N, int C, int64_t hw, int groups, const float *gamma, const float *beta,
                        float eps, const float *residual, int relu, float *y, void *workspace,

@@ -143,6 +143,9 @@ SIGNATURES = {
     "aoc_gct_scale_grad": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i64, _vp, _vp]),
     "aoc_cond_codes_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "aoc_cond_scale_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _vp]),
+    "aoc_groupnorm_relu_grad_workspace_bytes": (_sz, [_i, _i, _i]),
+    "aoc_groupnorm_relu_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "aoc_cat_film_scale_grad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _vp, _vp, _vp]),
 }
 
 STATUS = {0: "AOC_OK", -1: "AOC_ERR_INVALID_ARG", -2: "AOC_ERR_WORKSPACE", -3: "AOC_ERR_LAUNCH", -4: "AOC_ERR_UNSUPPORTED"}
