@@ -732,6 +732,68 @@ int aoc_groupnorm_relu_grad(const float *grad_y, const float *x, const float *re
 int aoc_cat_film_scale_grad(const float *grad_y, const float *x, const float *mem, const float *gain, int n_obj, int Cx, int Cm, int64_t hw, float *grad_x,
                             float *grad_mem, float *dgain, aoc_stream_t stream);
 
+/*
+ * Training-time decoder tail (csrc/tail_grad.hip; aoc_amd.tail_train): the backward of aoc_shortcut_stage_enqueue, the apply pass of a delta
+ * gate, the prediction head with the index of its background minimum, and their gradients.  fp32, no float atomics, every sum in an order
+ * fixed by the shapes and the pointers' 16-byte alignment; every pointer marked optional may be NULL and its work is skipped, and each
+ * optional output has the same bits alone as with the others; every argument is validated before the first launch, and a call that is
+ * rejected enqueues nothing.  N <= AOC_MAX_OBJECTS; planes ride on the grid's x axis (N * C up to 2^31 - 1).
+ *
+ * The shortcut stage, out = gain * cat(bicubic(x), low) with gain = 1 + tanh(W [IA_head | delta(px)] + b), px = the plane means of the
+ * concatenation, delta(px)[n] = sum_m px[m] - px[n] (decoding_module.py:163, 170-176).  grad_out [N, Ce + Cr, H, W]; x [N, Ce, h, w];
+ * low [N, Cr, H, W] (NULL with Cr = 0).
+ *
+ * aoc_shortcut_stage_grad_dots (pass A):
+ *   t[n, c] = U^T grad_out[n, c] [h, w]   the adjoint of the bicubic upsample alone, with aoc_bicubic_cat_scale's own weights (the integer
+ *       coordinate split, A = -0.75, clamped taps), in gather form: u[I, j] = sum over the output columns J in ascending order, the taps
+ *       k = 0..3 of each in turn, of wx[J][k] * grad_out[I, J] where clamp(ix(J) + k - 1) == j; then t[i, j] = the same over the output rows
+ *       I with wy and u.  Each product is rounded, then added, from 0.0f.  Clamped taps that land on one border pixel are all added; a
+ *       coarse pixel no tap reaches is 0.0f.  Written to t_out [N, Ce, h, w], or kept in the workspace when t_out == NULL.
+ *   dgain[n, c < Ce] = sum_ij x * t (= <grad_out, bicubic(x)>): grad_out is read once (plus the fine rows two neighbouring bands share) and
+ *       the upsample is never formed.  A workgroup owns a band of coarse rows: thread t of 256 adds x[f] * t[f] for the band's elements
+ *       f = t, t + 256, ... (row-major), the xor butterfly over a wave, the four wave sums in ascending order; then the bands in ascending
+ *       order from 0.0f.  The band height follows from (N * Ce, h, w, H, W) alone.
+ *   dgain[n, Ce + c] = the plane dot of grad_out[n, Ce + c] and low[n, c]: aoc_channel_scale_grad itself, called per object.
+ * dgain [N, Ce + Cr] is optional (needs x, and low when Cr >= 1).  The workspace is needed unless t_out is given and dgain is not.
+ *
+ * aoc_shortcut_stage_grad_apply (pass B), after aoc_film_gain_grad and the delta pull-back dpx[n] = sum_m dd[m] - dd[n] on [N, Ce + Cr]:
+ *   grad_x[n, c, i, j] = gain[n, c] * t + (cy[i] * cx[j]) * (dpx[n, c] / (float)(H W))     in place over t (grad_x holds t on entry)
+ *   grad_low[n, c, p]  = gain[n, Ce + c] * grad_out[n, Ce + c, p] + dpx[n, Ce + c] / (float)(H W)
+ * cy, cx = the column sums of the two 1-D interpolation matrices, formed as aoc_bicubic_plane_mean forms them.  gain == NULL is 1 and
+ * dpx == NULL is 0 (with both, a plain resize adjoint: grad_x is t).  grad_x and grad_low (needs Cr >= 1) are optional.  grad_low's planes are
+ * cut by their own alignment: up to three scalars in front, 16 bytes per lane, up to three scalars behind. */
+size_t aoc_shortcut_stage_grad_workspace_bytes(int N, int Ce, int h, int w, int H, int W);
+int aoc_shortcut_stage_grad_dots(const float *grad_out, const float *x, const float *low, int N, int Ce, int Cr, int h, int w, int H, int W, float *t_out,
+                                 float *dgain, void *workspace, size_t workspace_bytes, aoc_stream_t stream);
+int aoc_shortcut_stage_grad_apply(const float *grad_out, const float *gain, const float *dpx, int N, int Ce, int Cr, int h, int w, int H, int W, float *grad_x,
+                                  float *grad_low, aoc_stream_t stream);
+
+/* The apply pass of a delta gate, y = gain * x with gain = 1 + tanh(W [IA_head | delta(plane means of x)] + b) (decoding_module.py:126-130,
+ * :181-185), after aoc_channel_scale_grad (dgain), aoc_film_gain_grad and the delta pull-back:
+ *   grad_x[n, c, p] = gain[n, c] * grad_y[n, c, p] + dpx[n, c] / (float)hw        (dpx == NULL: no shift)
+ * 16 bytes per lane, the plane cut by grad_x's alignment; grad_y is read at 4-byte alignment. */
+int aoc_delta_gate_grad_apply(const float *grad_y, const float *gain, const float *dpx, int N, int C, int64_t hw, float *grad_x, aoc_stream_t stream);
+
+/* aoc_logit_head that also writes arg [hw] (int32): the object n >= 1 whose bg logit is the minimum.  The strict `<` of aoc_logit_head: the
+ * lowest n wins a tie, a NaN is never selected, and 0 stands for "no object" (every bg logit NaN or +inf).  With N = 1 arg is untouched (and
+ * may be NULL).  The channel sums are repeated term by term: pred is bit-equal to aoc_logit_head's. */
+int aoc_logit_head_argmin(const float *x, const float *wb_fg, const float *wb_bg, int64_t stride, int N, int C, int64_t hw, float *pred, int32_t *arg,
+                          aoc_stream_t stream);
+/* Its backward.  g = grad_pred [N, hw]; x [N, C, hw] (always needed: its planes' alignment cuts the sums); wfg, wbg = the first C columns of
+ * the rows of wb_fg, wb_bg.  Each output optional:
+ *   grad_x[n, c, p]     = g[n, p] * wfg[n, c] + (n == arg[p] ? g[0, p] * wbg[n, c] : 0)             (needs wb_fg, and wb_bg when N > 1)
+ *   grad_wb_fg[n, c]    = sum_p g[n, p] * x[n, c, p]                 grad_wb_fg[n, C] = sum_p g[n, p]
+ *   grad_wb_bg[n, c]    = sum_{p: arg[p] == n} g[0, p] * x[n, c, p]  grad_wb_bg[n, C] = sum_{p: arg[p] == n} g[0, p]     (n >= 1; row 0 is 0)
+ * grad_wb_* [N, C + 1] contiguous.  One workgroup per column (n, c): x is read once, grad_x written once.  The sums run in
+ * aoc_channel_scale_grad's order with the plane cut by x's alignment (by grad_pred[n]'s for the bias column) whatever is written; the pixels
+ * of other objects add +0.0f to a bg sum. */
+int aoc_logit_head_grad(const float *grad_pred, const int32_t *arg, const float *x, const float *wb_fg, const float *wb_bg, int64_t stride, int N, int C,
+                        int64_t hw, float *grad_x, float *grad_wb_fg, float *grad_wb_bg, aoc_stream_t stream);
+/* aoc_background_merge with the same arg [hw], and its backward: grad_fg = grad_pred; grad_bg[n, p] = (n == arg[p]) * grad_pred[0, p], row 0
+ * zero.  Both gradients optional. */
+int aoc_background_merge_argmin(const float *fg, const float *bg, int N, int64_t hw, float *pred, int32_t *arg, aoc_stream_t stream);
+int aoc_background_merge_grad(const float *grad_pred, const int32_t *arg, int N, int64_t hw, float *grad_fg, float *grad_bg, aoc_stream_t stream);
+
 /* ---- round 4: fused per-frame launches (each replaces several of the calls above and computes the same expressions term by term, so
  * the outputs equal theirs bit for bit; hotpath.proto_mask_features and aoc_frame_enqueue both use them) ---------------------------- */
 

@@ -146,6 +146,14 @@ SIGNATURES = {
     "aoc_groupnorm_relu_grad_workspace_bytes": (_sz, [_i, _i, _i]),
     "aoc_groupnorm_relu_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "aoc_cat_film_scale_grad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _vp, _vp, _vp]),
+    "aoc_shortcut_stage_grad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "aoc_shortcut_stage_grad_dots": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "aoc_shortcut_stage_grad_apply": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "aoc_delta_gate_grad_apply": (_i, [_vp, _vp, _vp, _i, _i, _i64, _vp, _vp]),
+    "aoc_logit_head_argmin": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i64, _vp, _vp, _vp]),
+    "aoc_logit_head_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i64, _vp, _vp, _vp, _vp]),
+    "aoc_background_merge_argmin": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp]),
+    "aoc_background_merge_grad": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp]),
 }
 
 STATUS = {0: "AOC_OK", -1: "AOC_ERR_INVALID_ARG", -2: "AOC_ERR_WORKSPACE", -3: "AOC_ERR_LAUNCH", -4: "AOC_ERR_UNSUPPORTED"}

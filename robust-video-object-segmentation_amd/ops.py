@@ -43,7 +43,9 @@ _TRAINABLE = {"global_matching_for_eval": "matching_train.global_matching", "glo
               "calculate_attention_head_for_eval_p_m": "frontend_train.calculate_attention_head_p_m",
               "IA_gate": "gates_train.IA_gate", "GCT": "gates_train.GCT", "conditioning_layer": "gates_train.conditioning_layer",
               "conditioning_block": "gates_train.conditioning_block",
-              "Bottleneck": "decoder_train.Bottleneck", "M1": "decoder_train.Modulator_1", "M2": "decoder_train.Modulator_2"}
+              "Bottleneck": "decoder_train.Bottleneck", "M1": "decoder_train.Modulator_1", "M2": "decoder_train.Modulator_2",
+              "decoder_final": "tail_train.decoder_final", "predict": "tail_train.predict",
+              "augment_background_logit": "tail_train.augment_background_logit"}
 
 
 def inference_only(what, *tensors):
@@ -52,8 +54,8 @@ def inference_only(what, *tensors):
     nothing, silently.  Raise instead when autograd is recording and an input or parameter wants a gradient.  The functions that do
     have a backward live in aoc_amd.matching_train (global_matching, global_matching_proxy), aoc_amd.local_train (local_matching,
     local_matching_proxy), aoc_amd.cluster_train (global_matching_cluster2), aoc_amd.frontend_train (foreground2background, the attention
-    heads, the aggregation), aoc_amd.gates_train (IA_gate, GCT, conditioning_layer, conditioning_block) and aoc_amd.decoder_train (Bottleneck,
-    Modulator_1, Modulator_2); the error text says so for them."""
+    heads, the aggregation), aoc_amd.gates_train (IA_gate, GCT, conditioning_layer, conditioning_block), aoc_amd.decoder_train (Bottleneck,
+    Modulator_1, Modulator_2) and aoc_amd.tail_train (decoder_final, predict, augment_background_logit); the error text says so for them."""
     if torch.is_grad_enabled():
         for t in tensors:
             if torch.is_tensor(t) and t.requires_grad:
