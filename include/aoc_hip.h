@@ -794,6 +794,64 @@ int aoc_logit_head_grad(const float *grad_pred, const int32_t *arg, const float 
 int aoc_background_merge_argmin(const float *fg, const float *bg, int N, int64_t hw, float *pred, int32_t *arg, aoc_stream_t stream);
 int aoc_background_merge_grad(const float *grad_pred, const int32_t *arg, int N, int64_t hw, float *grad_fg, float *grad_bg, aoc_stream_t stream);
 
+/*
+ * Training-time ASPP (csrc/aspp_grad.hip; aoc_amd.aspp_train): the backward of aoc_plane_sum_sumsq / aoc_gct_gate_multi /
+ * aoc_channel_scale_multi (aspp.py:19 four times, :46) and of aoc_groupnorm_cat_relu with the GCT behind it (aspp.py:21-23 four times,
+ * :61-65).  fp32, no float atomics, every sum in an order fixed by the shapes and the pointers' 16-byte alignment; every pointer marked
+ * optional may be NULL and its work is skipped, and each optional output has the same bits alone as with the others; every argument is
+ * validated before the first launch (outputs that overlap an input or each other: AOC_ERR_INVALID_ARG), and a call that is rejected enqueues
+ * nothing.  N <= AOC_MAX_OBJECTS; planes ride on the grid's x axis (up to 2^31 - 1); pointer lists are host arrays of 1 .. 8 device
+ * pointers (other counts: AOC_ERR_INVALID_ARG), as aoc_channel_scale_multi's.
+ *
+ * The front, v_k = x * gate_k(plane sums of x^2) for k < n_set and mean = sum x / hw:
+ *
+ * aoc_plane_dot_multi: dots[k, p] = sum_i g_k[p, i] * x[p, i] for the n_set gradient tensors g_k [planes, hw]; dots [n_set, planes].  Set k's
+ * plane is cut by g_k's own alignment and summed in aoc_channel_scale_grad's order, so set k is bit-equal to aoc_channel_scale_grad(g_k, x)
+ * with grad_x == NULL.  Where the sets share one cut, each 16 bytes of x are loaded once for all of them. */
+int aoc_plane_dot_multi(const float *x, const float *const *g_ptrs, int n_set, int64_t planes, int64_t hw, float *dots, aoc_stream_t stream);
+
+/* aoc_gct_gate_grad for n_set parameter sets over ONE [N, C] array of plane sums, one workgroup per set: dgate, gate [n_set, N, C]; alpha,
+ * gamma, beta [n_set, C] (beta is not read).  Set k of dsum [n_set, N, C] and of grad_alpha, grad_gamma, grad_beta [n_set, C] carries the
+ * bits of aoc_gct_gate_grad with row k; dsum_total [N, C] = sum_k dsum[k] in ascending k from 0.0f.  All five outputs are optional; the
+ * workspace is needed (AOC_ERR_WORKSPACE) only for dsum_total without dsum.  Both modes of aoc_gct_gate_grad (l1_mode) are supported. */
+size_t aoc_gct_gate_multi_grad_workspace_bytes(int n_set, int N, int C);
+int aoc_gct_gate_multi_grad(const float *dgate, const float *gate, const float *plane_sums, const float *alpha, const float *gamma, const float *beta,
+                            int n_set, int N, int C, float eps, int l1_mode, float *dsum_total, float *dsum, float *grad_alpha, float *grad_gamma,
+                            float *grad_beta, void *workspace, size_t workspace_bytes, aoc_stream_t stream);
+
+/* The apply pass of the front (l2 mode: d(sum x^2)/dx = 2 x):
+ *   grad_x[p, i] = ((sum_k g_k[p, i] * gates[k, p]) + (2 * dsum_total[p]) * x[p, i]) + dmean[p] / (float)hw
+ * in exactly this order: the sum over k starts from the product of set 0 and adds the sets in ascending k; then the second term; then,
+ * unless dmean == NULL, the mean's share.  2 * dsum_total is exact, so with n_set = 1 and dmean == NULL the result is bit-equal to
+ * aoc_gct_scale_grad in mode 1.  The plane is cut by grad_x's alignment; g_k and x are read 16 bytes per lane at any misalignment. */
+int aoc_channel_scale_multi_grad_apply(const float *const *g_ptrs, const float *gates, const float *x, const float *dsum_total, const float *dmean,
+                                       int n_set, int64_t planes, int64_t hw, float *grad_x, aoc_stream_t stream);
+
+/* The back: out = G[n, cc] * cat, cat = aoc_groupnorm_cat_relu(u_0 .. u_{n_src-1}, tail) with relu = 1, G = aoc_gct_gate(plane_sumsq of cat)
+ * in l2 mode.  grad_out [N, C_total, hw], C_total = n_src * C_src + C_tail; u_k [N, C_src, hw]; stats [n_src][N * groups][2] = (mean, rstd) as
+ * aoc_groupnorm_cat_relu leaves them at the start of its workspace; gamma, beta [n_src, C_src] or NULL (1, 0); tail [N, C_tail] (before its
+ * ReLU; NULL with C_tail = 0); plane_sumsq, gate [N, C_total]; gct_alpha, gct_gamma [C_total].  With z = u * a + b (a = rstd * gamma,
+ * b = beta - mean * a: the forward's own float expression), m = (z > 0), cat = max(z, 0), xhat = (u - mean) * rstd, M = (C_src / groups) * hw:
+ *   plane pass   P1 = sum g * cat   P2 = sum m ? g : 0   P3 = sum m ? g * xhat : 0   P4 = sum cat   P5 = sum cat * xhat     (source planes)
+ *                Sg = sum g,  P1 = relu(tail) * Sg                                                                           (tail planes)
+ *                one workgroup per plane of grad_out, the plane cut by grad_out's alignment, in aoc_channel_scale_grad's order
+ *   small        ds, grad_gct_alpha, grad_gct_gamma, grad_gct_beta = aoc_gct_gate_grad's arithmetic with dgate = P1
+ *                A = G * P2 + (2 * ds) * P4        B = G * P3 + (2 * ds) * P5
+ *                s1[k, n, g] = sum_{c in g} gamma_c * A     s2 likewise with B                                 (ascending c from 0.0f)
+ *                grad_gamma[k, c] = sum_n B        grad_beta[k, c] = sum_n A                                   (ascending n from 0.0f)
+ *                grad_tail[n, c] = tail > 0 ? G * Sg + ((2 * ds) * (float)hw) * tail : 0
+ *   apply pass   dz = m ? g * G + (2 * ds) * cat : 0        grad_u_k = rstd * ((gamma_c * dz - s1 / M) - xhat * (s2 / M)),  M as (float)M
+ *                the plane cut by grad_u_k's alignment
+ * grad_out and u are read twice, every gradient is written once, nothing of activation size is stored in between.  grad_u_ptrs (NULL, or a
+ * list of n_src pointers of which any may be NULL), grad_gamma, grad_beta [n_src, C_src], grad_tail [N, C_tail] and the three GCT gradients
+ * [C_total] are each optional.  The workspace (P, ds and (s1, s2) / M) is always needed: AOC_ERR_WORKSPACE when it is short. */
+size_t aoc_groupnorm_cat_relu_grad_workspace_bytes(int n_src, int N, int C_src, int C_tail, int groups);
+int aoc_groupnorm_cat_relu_grad(const float *grad_out, const float *const *u_ptrs, int n_src, int N, int C_src, int64_t hw, int groups, const float *stats,
+                                const float *gamma, const float *beta, const float *tail, int C_tail, const float *plane_sumsq, const float *gate,
+                                const float *gct_alpha, const float *gct_gamma, float gct_eps, float *const *grad_u_ptrs, float *grad_gamma,
+                                float *grad_beta, float *grad_tail, float *grad_gct_alpha, float *grad_gct_gamma, float *grad_gct_beta, void *workspace,
+                                size_t workspace_bytes, aoc_stream_t stream);
+
 /* ---- round 4: fused per-frame launches (each replaces several of the calls above and computes the same expressions term by term, so
  * the outputs equal theirs bit for bit; hotpath.proto_mask_features and aoc_frame_enqueue both use them) ---------------------------- */
 

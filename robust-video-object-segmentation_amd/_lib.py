@@ -154,6 +154,13 @@ SIGNATURES = {
     "aoc_logit_head_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i64, _vp, _vp, _vp, _vp]),
     "aoc_background_merge_argmin": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp]),
     "aoc_background_merge_grad": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp]),
+    "aoc_plane_dot_multi": (_i, [_vp, _vp, _i, _i64, _i64, _vp, _vp]),
+    "aoc_gct_gate_multi_grad_workspace_bytes": (_sz, [_i, _i, _i]),
+    "aoc_gct_gate_multi_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "aoc_channel_scale_multi_grad_apply": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _vp, _vp]),
+    "aoc_groupnorm_cat_relu_grad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "aoc_groupnorm_cat_relu_grad": (_i, [_vp, _vp, _i, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _vp, _sz, _vp]),
 }
 
 STATUS = {0: "AOC_OK", -1: "AOC_ERR_INVALID_ARG", -2: "AOC_ERR_WORKSPACE", -3: "AOC_ERR_LAUNCH", -4: "AOC_ERR_UNSUPPORTED"}

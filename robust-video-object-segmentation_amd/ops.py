@@ -45,7 +45,8 @@ _TRAINABLE = {"global_matching_for_eval": "matching_train.global_matching", "glo
               "conditioning_block": "gates_train.conditioning_block",
               "Bottleneck": "decoder_train.Bottleneck", "M1": "decoder_train.Modulator_1", "M2": "decoder_train.Modulator_2",
               "decoder_final": "tail_train.decoder_final", "predict": "tail_train.predict",
-              "augment_background_logit": "tail_train.augment_background_logit"}
+              "augment_background_logit": "tail_train.augment_background_logit",
+              "ASPP": "aspp_train.ASPP", "_ASPPModule": "aspp_train._ASPPModule"}
 
 
 def inference_only(what, *tensors):
@@ -55,7 +56,8 @@ def inference_only(what, *tensors):
     have a backward live in aoc_amd.matching_train (global_matching, global_matching_proxy), aoc_amd.local_train (local_matching,
     local_matching_proxy), aoc_amd.cluster_train (global_matching_cluster2), aoc_amd.frontend_train (foreground2background, the attention
     heads, the aggregation), aoc_amd.gates_train (IA_gate, GCT, conditioning_layer, conditioning_block), aoc_amd.decoder_train (Bottleneck,
-    Modulator_1, Modulator_2) and aoc_amd.tail_train (decoder_final, predict, augment_background_logit); the error text says so for them."""
+    Modulator_1, Modulator_2), aoc_amd.tail_train (decoder_final, predict, augment_background_logit) and aoc_amd.aspp_train (ASPP, _ASPPModule);
+    the error text says so for them."""
     if torch.is_grad_enabled():
         for t in tensors:
             if torch.is_tensor(t) and t.requires_grad:
