@@ -1270,6 +1270,67 @@ size_t aoc_gates_workspace_bytes(const aoc_gate_desc *gates, int n_gates, int n_
 int aoc_gates_enqueue(const aoc_gate_desc *gates, int n_gates, const float *head, int n_obj, int head_dim, void *workspace, size_t workspace_bytes,
                       aoc_stream_t stream);
 
+/*
+ * Training criterion (csrc/loss_grad.hip; aoc_amd.loss_train): aocnet.py:71-82 and Concat_CrossEntropyLoss (networks/layers/loss.py:52-97) for
+ * ONE sample, without the upsampled logits: bilinear upsample (align_corners=True) + per-pixel cross-entropy + argmax, the mean of the k
+ * hardest pixels, the mask of those pixels, and the gradient with respect to the coarse logits.  pred [C, h, w] float32, C = 1 .. 31 (other
+ * values: AOC_ERR_UNSUPPORTED); labels [H * W] int32; H * W and C * h * w below 2^31.  fp32, no float atomics, every float sum in an order
+ * fixed by the shapes (the same buffers give the same bits); every argument is validated before the first launch and a rejected call
+ * writes nothing; every pointer marked optional may be NULL, and each optional output has the same bits alone as with the others.
+ *
+ * The tap of fine index o on an axis of `in` coarse and `out` fine points (torch's upsample_bilinear2d, align_corners=True, in float):
+ *   scale = (float)(in - 1) / (float)(out - 1)  (0.0f when out == 1);  src = (float)o * scale;  i0 = min((int)src, in - 1);
+ *   i1 = min(i0 + 1, in - 1);  w1 = min(max(src - (float)i0, 0), 1);  w0 = 1.0f - w1
+ * and the logit x_c = w0y * (w0x * a + w1x * b) + w1y * (w0x * c + w1x * d), a, b the taps of row i0y and c, d of row i1y; a tap whose
+ * weight is exactly 0 is not multiplied in, so h == H and w == W hands the logits through bit for bit.
+ *
+ * aoc_upsample_ce_forward: m = max_c x_c (the lowest channel of a tie is argmax), lse = m + logf(sum_c expf(x_c - m)) with the channels in
+ * ascending order, loss = lse - x[label] (never negative).  A pixel whose label is ignore_index, or lies outside [0, C), gets loss +0.0f;
+ * the second kind is counted in bad[0] (an integer atomic into a word the call zeroes first).  valid_partial[b] = the pixels of
+ * [256 b, 256 b + 256) with a label in [0, C) other than ignore_index; aoc_upsample_ce_partials(H * W) entries.  loss, lse [H * W] float,
+ * argmax [H * W] int32, valid_partial, bad: all optional. */
+int64_t aoc_upsample_ce_partials(int64_t n);
+int aoc_upsample_ce_forward(const float *pred, const int32_t *labels, int C, int h, int w, int H, int W, int ignore_index, float *loss, float *lse,
+                            int32_t *argmax, int32_t *valid_partial, int32_t *bad, aoc_stream_t stream);
+/* aoc_topk_mean: loss [n] (n < 2^31), 1 <= k <= n (else AOC_ERR_INVALID_ARG) -> thr = the k-th largest value (a radix select over the
+ * monotone integer image of the floats: four passes of eight bits, many workgroups, integer histograms), n_gt = the number of values
+ * strictly above thr, mean = (S + (float)(k - n_gt) * thr) / (float)k with S the sum of the values above thr: contiguous chunks of
+ * max(4096, ceil(n / 1024) rounded up to 256) values; in a chunk thread t of 256 adds elements t, t + 256, ... in ascending order, the xor
+ * butterfly over a wave, the four wave sums in ascending order; then the chunks in ascending order from 0.0f.  A NaN is always added, so it
+ * makes mean NaN (nothing else is promised then).  mean, thr, n_gt are single device words, each optional.
+ * aoc_valid_mean (the reduction='mean' branch): mean = S / (float)n_valid, S over every value in the same order, n_valid = the sum of
+ * aoc_upsample_ce_forward's n_partial counts; 0 valid pixels give 0 / 0 = NaN, as torch does.  Workspace: aoc_topk_mean_workspace_bytes(n). */
+size_t aoc_topk_mean_workspace_bytes(int64_t n);
+int aoc_topk_mean(const float *loss, int64_t n, int64_t k, float *mean, float *thr, int32_t *n_gt, void *workspace, size_t workspace_bytes,
+                  aoc_stream_t stream);
+int aoc_valid_mean(const float *loss, int64_t n, const int32_t *valid_partial, int64_t n_partial, float *mean, int32_t *n_valid, void *workspace,
+                   size_t workspace_bytes, aoc_stream_t stream);
+/* aoc_topk_select_mask: mask[p] (one byte, 0 / 1) = loss[p] > thr, or loss[p] == thr and fewer than k - n_gt pixels of that value stand at
+ * lower indices: the lowest index wins a tie, and exactly k bytes are set.  thr, n_gt: the device words aoc_topk_mean wrote.
+ * aoc_valid_mask (the reduction='mean' branch): mask[p] = labels[p] != ignore_index and lies in [0, C). */
+size_t aoc_topk_select_mask_workspace_bytes(int64_t n);
+int aoc_topk_select_mask(const float *loss, int64_t n, int64_t k, const float *thr, const int32_t *n_gt, uint8_t *mask, void *workspace,
+                         size_t workspace_bytes, aoc_stream_t stream);
+int aoc_valid_mask(const int32_t *labels, int64_t n, int C, int ignore_index, uint8_t *mask, aoc_stream_t stream);
+/* aoc_criterion_forward: the forward of one sample as ONE call: aoc_upsample_ce_forward, then aoc_topk_mean and aoc_topk_select_mask (k >= 1) or
+ * aoc_valid_mean and aoc_valid_mask (k == 0), exactly those launches with thr, n_gt and the valid counts kept in the workspace, so every output
+ * has the bits of the separate calls.  loss [H * W] and mean are required; lse, argmax, mask [H * W] bytes, n_valid (written when k == 0) and bad
+ * are optional.  Every argument is validated before the first launch. */
+size_t aoc_criterion_forward_workspace_bytes(int64_t n);
+int aoc_criterion_forward(const float *pred, const int32_t *labels, int C, int h, int w, int H, int W, int ignore_index, int64_t k, float *loss, float *lse,
+                          int32_t *argmax, uint8_t *mask, float *mean, int32_t *n_valid, int32_t *bad, void *workspace, size_t workspace_bytes,
+                          aoc_stream_t stream);
+/* aoc_upsample_ce_grad: grad_pred [C, h, w] = U^T[ mask * scale * (softmax - onehot) ], scale = grad_out[0] / (float)k (k >= 1) or
+ * grad_out[0] / (float)n_valid[0] (k == 0); grad_out, n_valid are device words, so nothing synchronises.  softmax_c = expf(x_c - lse) with
+ * x_c by the forward's own expression, g = scale * (softmax_c - 1.0f) at the label's channel and scale * softmax_c elsewhere; pixels whose
+ * label is ignore_index or out of range contribute nothing even when the mask selects them.  The adjoint is in gather form: a workgroup
+ * owns a band of coarse rows of one channel (the channels are independent once lse is known); u[I, j] adds the fine columns J in ascending
+ * order, tap 0 then tap 1 of each, grad[i, j] the fine rows I in ascending order likewise, each product rounded and then added from 0.0f; a
+ * tap of weight 0 is skipped as in the forward.  A coarse pixel no fine pixel reaches is written as 0.  Nothing of size C * H * W is
+ * written and no workspace is needed. */
+int aoc_upsample_ce_grad(const float *pred, const int32_t *labels, const float *lse, const uint8_t *mask, const float *grad_out, int64_t k,
+                         const int32_t *n_valid, int C, int h, int w, int H, int W, int ignore_index, float *grad_pred, aoc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

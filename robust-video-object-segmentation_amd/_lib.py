@@ -161,6 +161,17 @@ SIGNATURES = {
     "aoc_groupnorm_cat_relu_grad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "aoc_groupnorm_cat_relu_grad": (_i, [_vp, _vp, _i, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                          _vp, _sz, _vp]),
+    "aoc_upsample_ce_partials": (_i64, [_i64]),
+    "aoc_upsample_ce_forward": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "aoc_topk_mean_workspace_bytes": (_sz, [_i64]),
+    "aoc_topk_mean": (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "aoc_valid_mean": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "aoc_topk_select_mask_workspace_bytes": (_sz, [_i64]),
+    "aoc_topk_select_mask": (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "aoc_valid_mask": (_i, [_vp, _i64, _i, _i, _vp, _vp]),
+    "aoc_criterion_forward_workspace_bytes": (_sz, [_i64]),
+    "aoc_criterion_forward": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "aoc_upsample_ce_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
 }
 
 STATUS = {0: "AOC_OK", -1: "AOC_ERR_INVALID_ARG", -2: "AOC_ERR_WORKSPACE", -3: "AOC_ERR_LAUNCH", -4: "AOC_ERR_UNSUPPORTED"}
