@@ -440,6 +440,21 @@ int aoc_dense_prune_stats_ex(uint64_t *out8, int reset);
  * Process-wide, may be changed between calls.  (The library itself never reads the environment.) */
 int aoc_set_stream_cus(int n_cus);
 
+/* The dense share.  The matrix kernel of aoc_dense_match_min_split runs as G RESIDENT workgroups, one per CU, that walk the work list of
+ * (512-pixel query block, tile split) items; G = the stream's CU budget (aoc_set_stream_cus / aoc_frame_desc.stream_cus, else 256) times
+ * share_256 / 256, rounded down to a multiple of 8 (from 8 up), at least 1, at most the number of items.  The CUs it leaves out stay
+ * free, for the whole launch, for what other streams enqueue (a resident dense workgroup fills a CU: nothing else runs beside it).  The
+ * split count is chosen for G: the splits that fill whole rounds of G best, over up to three rounds (two at share 256, the rule of the
+ * one-workgroup-per-item kernel).  Results do not depend on the share, bit for bit.
+ * share_256 in 1 .. 256; process-wide, may be changed between calls; never read from the environment.  AOC_DENSE_SHARE_DEFAULT is what
+ * a process starts with (DESIGN.md section 4.4 has the sweep that chose it). */
+#define AOC_DENSE_SHARE_DEFAULT 224
+int aoc_set_dense_share(int share_256);
+int aoc_dense_share(void);
+/* The sizing above as a function: m query pixels, budget CUs (0 = 256), share_256 -> the split count, the items (query blocks x
+ * splits) and the resident workgroups G of the launch. */
+int aoc_dense_split_sizing(int64_t m, int budget, int share_256, int32_t *splits, int32_t *items, int32_t *workgroups);
+
 /* Measurement probe: the NEXT aoc_dense_match_min / aoc_dense_match_min_split call made by the calling thread records
  * `start` immediately before and `stop` immediately after its matrix kernel (dense_match_partial_kernel /
  * dense_prune_kernel) on the call's stream, then the probe is cleared.  Both are hipEvent_t created by the caller

@@ -59,6 +59,9 @@ SIGNATURES = {
     "aoc_proxy_corr_min_f16": (_i, [_vp, _i64, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64, _i, _vp]),
     "aoc_dense_match_set_probe": (_i, [_vp, _vp]),
     "aoc_set_stream_cus": (_i, [_i]),
+    "aoc_set_dense_share": (_i, [_i]),
+    "aoc_dense_share": (_i, []),
+    "aoc_dense_split_sizing": (_i, [_i64, _i, _i, _vp, _vp, _vp]),
     "aoc_split_record_bytes": (_sz, [_i]),
     "aoc_split_rows": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp]),
     "aoc_split_rows_tiled_bytes": (_sz, [_i64, _i]),

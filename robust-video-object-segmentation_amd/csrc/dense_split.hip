@@ -261,7 +261,7 @@ constexpr int SP_TILE_SLACK = 2;                                  // the plan al
 
 // Coarse-then-rescore.  Block = 8 waves x 2 query tiles (512 query pixels; both planes of their records are the stationary B
 // operands, 112 VGPR); the object-sorted reference tiles stream through two LDS chunk buffers (8 tiles each, hi planes only; A operands).
-// Grid = (query blocks, tile splits).  Per (reference tile, query tile) ONE pass of 7 MFMAs gives
+// Work list = (query blocks, tile splits), walked by a grid of resident workgroups (see the item loop).  Per (reference tile, query tile) ONE pass of 7 MFMAs gives
 // coarse = 2^20 (qh.rh - |r|^2/2); the exact three-product value differs from it by the qh.rl + ql.rh terms, bounded by
 // eps(q) = 2^10 |q| max|r| (1 + margins): a pair whose coarse value plus eps is below the best EXACT value already known for that
 // (query pixel, object) cannot hold the maximum and is skipped; any other pair gets the 14 MFMAs of the two cross terms added onto the
@@ -301,7 +301,7 @@ __global__ __launch_bounds__(SP_NW * 64, 1) void dense_prune_kernel(const uint4 
                                                                      const uint4 *__restrict__ prec, const int32_t *__restrict__ tile_rows,
                                                                      const int32_t *__restrict__ tile_obj, const int32_t *__restrict__ n_tiles_ptr,
                                                                      const int32_t *__restrict__ gate, const uint32_t *__restrict__ pmax_bits,
-                                                                     int n_obj, uint32_t *__restrict__ gbest, int q_tiled) {
+                                                                     int n_obj, uint32_t *__restrict__ gbest, int q_tiled, int n_split) {
     if (*gate) return;
     extern __shared__ __attribute__((aligned(16))) uint4 lds4[];
     // Swizzle of the unpadded LDS rows: chunk c of row r sits at position c ^ ((r >> 3) & SWZ_MASK).  A ds_read_b128 is served in groups of 16 lanes
@@ -315,278 +315,293 @@ __global__ __launch_bounds__(SP_NW * 64, 1) void dense_prune_kernel(const uint4 
     const uint32_t lds_base = (uint32_t)reinterpret_cast<uintptr_t>(lds4);
     const char *lds_bytes = reinterpret_cast<const char *>(lds4);
 
-    // XCD-aware block -> (query block, tile split) map: workgroups are dealt round-robin to the 8 XCDs, each with its own
-    // L2; give every XCD a contiguous range of the (split-major) work list so that the ~gridDim.x blocks that stream the
-    // same reference tiles share one L2 instead of pulling them through all eight
-    int bx, by;
-    {
-        const int nb = gridDim.x * gridDim.y, lin = blockIdx.y * gridDim.x + blockIdx.x;
-        const int xcd = lin & 7, slot = lin >> 3, q = nb >> 3, r = nb & 7;
-        const int v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-        by = v / gridDim.x;
-        bx = v - by * gridDim.x;
-    }
-    // split `by` owns the tiles by, by + ns, by + 2 ns, ...: every split sees the same mix of objects (small objects rescore far more often
-    // than the background; contiguous ranges would leave all of that work to the last splits, i.e. to one XCD)
+    // The work list: items (query block bx, tile split by), nbx x n_split of them, split-major.  The grid is G RESIDENT workgroups (one per CU
+    // of the share of the stream's CUs that aoc_dense_split_sizing gives this kernel); workgroup w walks the items lin = w, w + G, w + 2 G, ...
+    // Per item everything starts over: the stationary query operands, the LDS ring, the bounds (those live in gbest and are shared anyway).
     const int n_tiles = *n_tiles_ptr;
-    const int ns = gridDim.y;
-    if (by >= n_tiles) return;
-    const int n_mine = (n_tiles - by + ns - 1) / ns;
-    const int n_chunks = (n_mine + SP_NB_HI - 1) / SP_NB_HI;
-
-    const int lane = aoc_lane(), wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int col = lane & 31, h = lane >> 5;
-    const int64_t wave_row0 = (int64_t)bx * (SP_NW * SP_NQ * 32) + (int64_t)wave * (SP_NQ * 32);
-
-    // ---- stationary query operands (both planes) and the per-pixel rescoring margin
-    const float pmax = sqrtf(__uint_as_float(*pmax_bits)) * 1.001f;
-    const float plmax = __uint_as_float(*(pmax_bits - 2));
-    f16x8 bh[SP_NQ][SP_KS], bl[SP_NQ][SP_KS];
-    float eps[SP_NQ];
-    bool valid[SP_NQ];
-#pragma unroll
-    for (int iq = 0; iq < SP_NQ; ++iq) {
-        const int64_t row = wave_row0 + iq * 32 + col;
-        valid[iq] = row < m;
-        // row-major records: chunk (plane, ks, h) of row r at r * 28 + plane * 14 + ks * 2 + h; tile-major (aoc_split_rows_tiled): per
-        // (32-row tile, plane, ks) the 64 chunks [h][row % 32] -- one coalesced 1 KiB wave load per operand
-        const int64_t rr = valid[iq] ? row : 0;
-        const uint4 *r = q_tiled ? qrec + (size_t)(rr >> 5) * (2 * SP_KS * 64) + h * 32 + (rr & 31) : qrec + (size_t)rr * SP_REC + h;
-        const int ks_step = q_tiled ? 64 : 2, plane_step = q_tiled ? SP_KS * 64 : SP_HALF;
-#pragma unroll
-        for (int ks = 0; ks < SP_KS; ++ks) {
-            uint4 u = r[ks * ks_step], v = r[plane_step + ks * ks_step];
-            if (!valid[iq]) { u = make_uint4(0, 0, 0, 0); v = make_uint4(0, 0, 0, 0); }
-            bh[iq][ks] = __builtin_bit_cast(f16x8, u);
-            bl[iq][ks] = __builtin_bit_cast(f16x8, v);
-        }
-        // norm slots: the query side holds the constant 2^15 (its own norm pieces sit in the record for when the
-        // frame later joins the pool); everything else past the channels is zero on both planes
-        const float ql_own = (float)bh[iq][SP_KS - 1][SP_NORM_SLOT % 16 + 3];      // lanes h == 0: the norm of the query pixel's own lo plane
-        if (h == 0) {
-            bh[iq][SP_KS - 1][SP_NORM_SLOT % 16 + 3] = (_Float16)0.0f;
-            bh[iq][SP_KS - 1][SP_NORM_SLOT % 16] = (_Float16)SP_QCONST;
-            bh[iq][SP_KS - 1][SP_NORM_SLOT % 16 + 1] = (_Float16)SP_QCONST;
-            bh[iq][SP_KS - 1][SP_NORM_SLOT % 16 + 2] = (_Float16)SP_QCONST;
-        } else {
-            // slots 104 / 105 (reserved, zero in records written by this build): multiplied by zero whatever an older record holds there
-            bh[iq][SP_KS - 1][0] = (_Float16)0.0f;
-            bh[iq][SP_KS - 1][1] = (_Float16)0.0f;
-        }
-        // |exact - coarse| = |qh.rl + ql.rh| <= |qh| |rl| + |ql| |rh| (Euclidean norms of the planes, Cauchy-Schwarz) with |qh| <= 2^10 |q|
-        // (1 + 2^-11), the lo norms as the records carry them (rounded up) and the maxima over the kept reference pixels, plus the
-        // roundings of 14 more accumulations
-        const float qn = valid[iq] ? sqrtf(q2[row]) : 0.0f;
-        const float ql = valid[iq] ? __shfl(ql_own, col) : 0.0f;
-        // (+ 0.0f: the place of the removed checkpoint's term.  The compiler may not fold it (-0), and without it the prologue is scheduled
-        // differently; it stays so that the instruction stream is the measured one)
-        eps[iq] = 1026.0f * (qn * plmax + ql * pmax) + 8.0f * pmax * pmax + 0.0f + 8.0f;
-    }
-
-    // ---- DMA plan of this wave: transfer k of a chunk fills the LDS slots [64 (7 wave + k), +64); slot j holds row j / 14, position j % 14.
-    // Packed per transfer: row of the chunk (0..255) in the high half, source byte offset of that position's chunk in the low half.
-    uint32_t dma_plan[SP_DMA_PER_WAVE];
-#pragma unroll
-    for (int k = 0; k < SP_DMA_PER_WAVE; ++k) {
-        const int j = (wave * SP_DMA_PER_WAVE + k) * 64 + lane;
-        const int r = j / SP_ROW_CHUNKS, pos = j - r * SP_ROW_CHUNKS;
-        dma_plan[k] = ((uint32_t)r << 16) | (uint32_t)((pos ^ ((r >> 3) & SWZ_MASK)) * 16);
-    }
-    const char *prec_bytes = reinterpret_cast<const char *>(prec);
-    auto dma_meta = [&](int chunk) {            // row ids (one wave) and tile objects (one wave) of a chunk -> their rings
-        // tile i of the split is tile by + i ns of the plan; past the end everything reads the (always present) empty tile n_tiles
-        const int i0 = chunk * SP_NB_HI;
-        // eight tiles x 32 ids = 1 KiB: ONE 16-byte transfer of one wave (lane -> tile lane / 8, ids 4 (lane % 8) .. + 3)
-        if (wave == W_ID0) {
-            const int t = min(by + (i0 + (lane >> 3)) * ns, n_tiles);
-            glds16(tile_rows + (size_t)t * SP_TILE + (lane & 7) * 4, lds_base + SP_IDS_OFF + (chunk % SP_IDS_SLOTS) * SP_IDS_SLOT_BYTES);
-        }
-        if (wave == W_OBJ) glds4(tile_obj + min(by + (i0 + (lane & (SP_NB_HI - 1))) * ns, n_tiles), lds_base + SP_OBJ_OFF + (chunk & 3) * 256);
-    };
-    auto dma_rows = [&](int chunk) {            // the chunk's hi planes -> buffer chunk % 2 (its ids must have landed and been published)
-        const int32_t *ids = reinterpret_cast<const int32_t *>(lds_bytes + SP_IDS_OFF + (chunk % SP_IDS_SLOTS) * SP_IDS_SLOT_BYTES);
-        const uint32_t dst = lds_base + (uint32_t)(chunk % SP_NBUF) * SP_CHUNK_BYTES + (uint32_t)(wave * SP_DMA_PER_WAVE) * 1024u;
-        int id[SP_DMA_PER_WAVE];
-#pragma unroll
-        for (int k = 0; k < SP_DMA_PER_WAVE; ++k) id[k] = ids[dma_plan[k] >> 16];      // all LDS reads before the first (ordering) asm statement
-#pragma unroll
-        for (int k = 0; k < SP_DMA_PER_WAVE; ++k)
-            glds16(prec_bytes + (size_t)(uint32_t)max(id[k], 0) * (SP_REC * 16) + (dma_plan[k] & 0xffffu), dst + (uint32_t)k * 1024u);
-    };
-
-    // best[iq]: best exact value this lane has produced for the current object; shared[iq]: the best anybody has published
-    float best[SP_NQ], shared[SP_NQ];
-    uint32_t grow[SP_NQ];                          // grow: word index of (pixel, object 0) in gbest (pixel 0 for rows past the end)
-#pragma unroll
-    for (int iq = 0; iq < SP_NQ; ++iq) {
-        grow[iq] = valid[iq] ? (uint32_t)(wave_row0 + iq * 32 + col) * (uint32_t)n_obj : 0u;
-        best[iq] = INFINITY;
-        shared[iq] = INFINITY;
-    }
-    int cur = -1;
+    const int ns = n_split;
+    const int nbx = (int)((m + SP_ROWS_PER_BLOCK - 1) / SP_ROWS_PER_BLOCK), nb = nbx * ns;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     unsigned n_rescored = 0, n_any = 0, n_seen = 0;
-    // what the other workgroups have published for the current object: one 4-byte transfer per query tile into this wave's own LDS
-    // words, read back one step later (device-scope load: the values come from L2, not from this CU's vector cache)
-    auto dma_bound = [&]() {
-#pragma unroll
-        for (int iq = 0; iq < SP_NQ; ++iq) {
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off sc1\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(gbest + grow[iq] + max(cur, 0)), "s"(lds_base + SP_BND_OFF + (uint32_t)(wave * SP_NQ + iq) * 256u) : "memory");
-        }
-    };
-    auto switch_object = [&](int o) {
-        cur = o;
-        uint32_t u[SP_NQ];
-#pragma unroll
-        for (int iq = 0; iq < SP_NQ; ++iq) u[iq] = load_relaxed(gbest + grow[iq] + cur);
-#pragma unroll
-        for (int iq = 0; iq < SP_NQ; ++iq) {
-            best[iq] = valid[iq] ? -INFINITY : INFINITY;         // rows past the end never ask for a rescoring
-            shared[iq] = valid[iq] ? ord_dec(u[iq]) : INFINITY;
-        }
-    };
-
-    // ---- prologue: meta of chunks 0 and 1, rows of chunk 0 (drained: once per workgroup)
-    dma_meta(0);
-    dma_meta(1);
-    __builtin_amdgcn_s_waitcnt(0x0f70);                           // vmcnt(0)
-    __builtin_amdgcn_s_barrier();
-    dma_rows(0);
-    __builtin_amdgcn_s_waitcnt(0x0f70);
-    __builtin_amdgcn_s_barrier();
-
-    // A fragment addressing: chunk index e + h (e even, compile time) of row (tile, col) sits at position (e & ~1) + (h ^ x),
-    // x = (col >> 3) & 1: one per-lane byte offset covers it
-    const int xs = (col >> 3) & SWZ_MASK;
-    const uint32_t row_off = (uint32_t)col * SP_ROW_BYTES;
-    const uint32_t sw0 = row_off + (uint32_t)((h ^ xs) * 16), sw2 = sw0 + 32u;
-    auto frag = [&](const char *tile_base, int e) -> f16x8 {       // e: even chunk index (2 ks)
-        const uint32_t off = ((e & 2) ? sw2 : sw0) + (uint32_t)((e & ~3) * 16);
-        return __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4 *>(tile_base + off));
-    };
-    auto ks_of = [&](int kk) { return (kk + SP_KS - 1) % SP_KS; };  // norm slots first: partial sums stay small
-
-    for (int s = 0; s < n_chunks; ++s) {
-        // (a) prefetches for the next step: published bounds of the current object, meta of chunk s + 2, rows of chunk s + 1 (whose ids
-        // the barrier that ended step s - 1 published)
-        const int4 objs = *reinterpret_cast<const int4 *>(lds_bytes + SP_OBJ_OFF + (s & 3) * 256);
-        const int4 objs_b = *reinterpret_cast<const int4 *>(lds_bytes + (s & 3) * 256 + SP_OBJ_OFF + 16);      // tiles 4..7
-        const int bound_obj = cur;
-        dma_bound();
-        dma_meta(s + 2);
-        dma_rows(s + 1);
-
-        // (b) the eight tiles of chunk s
-        const char *chunk_base = lds_bytes + (s % SP_NBUF) * SP_CHUNK_BYTES;
-        const int n_here = min(SP_NB_HI, n_mine - s * SP_NB_HI);
-        // the first two A fragments of a tile are requested while the previous tile's epilogue runs
-        f16x8 pre0 = frag(chunk_base, 2 * ks_of(0)), pre1 = frag(chunk_base, 2 * ks_of(1));
-        // the tiles' objects in one 64-bit scalar (objects are < 256): two SALU operations per tile instead of a chain of selects
-        const uint32_t objs_lo = (uint32_t)__builtin_amdgcn_readfirstlane((objs.x & 0xff) | ((objs.y & 0xff) << 8) | ((objs.z & 0xff) << 16) | ((objs.w & 0xff) << 24));
-        const uint32_t objs_hi = (uint32_t)__builtin_amdgcn_readfirstlane((objs_b.x & 0xff) | ((objs_b.y & 0xff) << 8) | ((objs_b.z & 0xff) << 16) | ((objs_b.w & 0xff) << 24));
-        const uint64_t objs_packed = ((uint64_t)objs_hi << 32) | objs_lo;
-        // the current chunk's row ids (the rescoring path addresses the lo planes in global memory with them)
-        const int32_t *ids_now = reinterpret_cast<const int32_t *>(lds_bytes + SP_IDS_OFF + (s % SP_IDS_SLOTS) * SP_IDS_SLOT_BYTES);
 #pragma unroll 1
-        for (int t = 0; t < n_here; ++t) {
-            const char *tile_base = chunk_base + t * SP_TILE_BYTES;
-            const int o = (int)((objs_packed >> (8 * t)) & 0xffu);
-            if (o != cur) switch_object(o);
-            // coarse pass: 7 k-steps x 2 query tiles, A fragments two k-steps ahead through a ring of three
-            f32x16 acc[SP_NQ];
+    for (int lin = blockIdx.x; lin < nb; lin += gridDim.x) {
+        // The lane index is made opaque once per item: what an item derives from it (operand addresses, the DMA plan, the fragment offsets) is then
+        // computed inside the item and dies there, as in a kernel that runs one item; hoisted out of this loop those values stay live across the tile loop
+        // and the kernel no longer fits the 256 registers of two waves per SIMD (it spills).
+        int lane = aoc_lane();
+        asm volatile("" : "+v"(lane));
+        const int col = lane & 31, h = lane >> 5;
+        const float pmax = sqrtf(__uint_as_float(*pmax_bits)) * 1.001f;
+        const float plmax = __uint_as_float(*(pmax_bits - 2));
+        // XCD-aware item -> (query block, tile split) map: workgroups are dealt round-robin to the 8 XCDs, each with its own
+        // L2; give every XCD a contiguous range of the (split-major) work list so that the ~nbx workgroups that stream the
+        // same reference tiles share one L2 instead of pulling them through all eight.  G is a multiple of 8 (when it is 8 or more), so
+        // lin & 7 is the same for every item of a workgroup: it stays inside its XCD's range.
+        int bx, by;
+        {
+            const int xcd = lin & 7, slot = lin >> 3, q = nb >> 3, r = nb & 7;
+            const int v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+            by = v / nbx;
+            bx = v - by * nbx;
+        }
+        // split `by` owns the tiles by, by + ns, by + 2 ns, ...: every split sees the same mix of objects (small objects rescore far more often
+        // than the background; contiguous ranges would leave all of that work to the last splits, i.e. to one XCD)
+        if (by >= n_tiles) continue;              // (uniform over the workgroup: no barrier is skipped by a part of it)
+        const int n_mine = (n_tiles - by + ns - 1) / ns;
+        const int n_chunks = (n_mine + SP_NB_HI - 1) / SP_NB_HI;
+
+        const int64_t wave_row0 = (int64_t)bx * (SP_NW * SP_NQ * 32) + (int64_t)wave * (SP_NQ * 32);
+
+        // ---- stationary query operands (both planes) and the per-pixel rescoring margin
+        f16x8 bh[SP_NQ][SP_KS], bl[SP_NQ][SP_KS];
+        float eps[SP_NQ];
+        bool valid[SP_NQ];
 #pragma unroll
-            for (int iq = 0; iq < SP_NQ; ++iq)
+        for (int iq = 0; iq < SP_NQ; ++iq) {
+            const int64_t row = wave_row0 + iq * 32 + col;
+            valid[iq] = row < m;
+            // row-major records: chunk (plane, ks, h) of row r at r * 28 + plane * 14 + ks * 2 + h; tile-major (aoc_split_rows_tiled): per
+            // (32-row tile, plane, ks) the 64 chunks [h][row % 32] -- one coalesced 1 KiB wave load per operand
+            const int64_t rr = valid[iq] ? row : 0;
+            const uint4 *r = q_tiled ? qrec + (size_t)(rr >> 5) * (2 * SP_KS * 64) + h * 32 + (rr & 31) : qrec + (size_t)rr * SP_REC + h;
+            const int ks_step = q_tiled ? 64 : 2, plane_step = q_tiled ? SP_KS * 64 : SP_HALF;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc[iq][r] = 0.0f;
-            {
-                f16x8 af[3];
-                af[0] = pre0;
-                af[1] = pre1;
-#pragma unroll
-                for (int kk = 0; kk < SP_KS; ++kk) {
-                    if (kk + 2 < SP_KS) af[(kk + 2) % 3] = frag(tile_base, 2 * ks_of(kk + 2));
-#pragma unroll
-                    for (int iq = 0; iq < SP_NQ; ++iq)
-                        acc[iq] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[kk % 3], bh[iq][ks_of(kk)], acc[iq], 0, 0, 0);
-                }
-                if (t + 1 < n_here) {
-                    pre0 = frag(tile_base + SP_TILE_BYTES, 2 * ks_of(0));
-                    pre1 = frag(tile_base + SP_TILE_BYTES, 2 * ks_of(1));
-                }
+            for (int ks = 0; ks < SP_KS; ++ks) {
+                uint4 u = r[ks * ks_step], v = r[plane_step + ks * ks_step];
+                if (!valid[iq]) { u = make_uint4(0, 0, 0, 0); v = make_uint4(0, 0, 0, 0); }
+                bh[iq][ks] = __builtin_bit_cast(f16x8, u);
+                bl[iq][ks] = __builtin_bit_cast(f16x8, v);
             }
-            // which query tiles may hold a new maximum (wave-uniform)
-            bool want[SP_NQ];
+            // norm slots: the query side holds the constant 2^15 (its own norm pieces sit in the record for when the
+            // frame later joins the pool); everything else past the channels is zero on both planes
+            const float ql_own = (float)bh[iq][SP_KS - 1][SP_NORM_SLOT % 16 + 3];      // lanes h == 0: the norm of the query pixel's own lo plane
+            if (h == 0) {
+                bh[iq][SP_KS - 1][SP_NORM_SLOT % 16 + 3] = (_Float16)0.0f;
+                bh[iq][SP_KS - 1][SP_NORM_SLOT % 16] = (_Float16)SP_QCONST;
+                bh[iq][SP_KS - 1][SP_NORM_SLOT % 16 + 1] = (_Float16)SP_QCONST;
+                bh[iq][SP_KS - 1][SP_NORM_SLOT % 16 + 2] = (_Float16)SP_QCONST;
+            } else {
+                // slots 104 / 105 (reserved, zero in records written by this build): multiplied by zero whatever an older record holds there
+                bh[iq][SP_KS - 1][0] = (_Float16)0.0f;
+                bh[iq][SP_KS - 1][1] = (_Float16)0.0f;
+            }
+            // |exact - coarse| = |qh.rl + ql.rh| <= |qh| |rl| + |ql| |rh| (Euclidean norms of the planes, Cauchy-Schwarz) with |qh| <= 2^10 |q|
+            // (1 + 2^-11), the lo norms as the records carry them (rounded up) and the maxima over the kept reference pixels, plus the
+            // roundings of 14 more accumulations
+            const float qn = valid[iq] ? sqrtf(q2[row]) : 0.0f;
+            const float ql = valid[iq] ? __shfl(ql_own, col) : 0.0f;
+            // (+ 0.0f: the place of the removed checkpoint's term.  The compiler may not fold it (-0), and without it the prologue is scheduled
+            // differently; it stays so that the instruction stream is the measured one)
+            eps[iq] = 1026.0f * (qn * plmax + ql * pmax) + 8.0f * pmax * pmax + 0.0f + 8.0f;
+        }
+
+        // ---- DMA plan of this wave: transfer k of a chunk fills the LDS slots [64 (7 wave + k), +64); slot j holds row j / 14, position j % 14.
+        // Packed per transfer: row of the chunk (0..255) in the high half, source byte offset of that position's chunk in the low half.
+        uint32_t dma_plan[SP_DMA_PER_WAVE];
+#pragma unroll
+        for (int k = 0; k < SP_DMA_PER_WAVE; ++k) {
+            const int j = (wave * SP_DMA_PER_WAVE + k) * 64 + lane;
+            const int r = j / SP_ROW_CHUNKS, pos = j - r * SP_ROW_CHUNKS;
+            dma_plan[k] = ((uint32_t)r << 16) | (uint32_t)((pos ^ ((r >> 3) & SWZ_MASK)) * 16);
+        }
+        const char *prec_bytes = reinterpret_cast<const char *>(prec);
+        auto dma_meta = [&](int chunk) {            // row ids (one wave) and tile objects (one wave) of a chunk -> their rings
+            // tile i of the split is tile by + i ns of the plan; past the end everything reads the (always present) empty tile n_tiles
+            const int i0 = chunk * SP_NB_HI;
+            // eight tiles x 32 ids = 1 KiB: ONE 16-byte transfer of one wave (lane -> tile lane / 8, ids 4 (lane % 8) .. + 3)
+            if (wave == W_ID0) {
+                const int t = min(by + (i0 + (lane >> 3)) * ns, n_tiles);
+                glds16(tile_rows + (size_t)t * SP_TILE + (lane & 7) * 4, lds_base + SP_IDS_OFF + (chunk % SP_IDS_SLOTS) * SP_IDS_SLOT_BYTES);
+            }
+            if (wave == W_OBJ) glds4(tile_obj + min(by + (i0 + (lane & (SP_NB_HI - 1))) * ns, n_tiles), lds_base + SP_OBJ_OFF + (chunk & 3) * 256);
+        };
+        auto dma_rows = [&](int chunk) {            // the chunk's hi planes -> buffer chunk % 2 (its ids must have landed and been published)
+            const int32_t *ids = reinterpret_cast<const int32_t *>(lds_bytes + SP_IDS_OFF + (chunk % SP_IDS_SLOTS) * SP_IDS_SLOT_BYTES);
+            const uint32_t dst = lds_base + (uint32_t)(chunk % SP_NBUF) * SP_CHUNK_BYTES + (uint32_t)(wave * SP_DMA_PER_WAVE) * 1024u;
+            int id[SP_DMA_PER_WAVE];
+#pragma unroll
+            for (int k = 0; k < SP_DMA_PER_WAVE; ++k) id[k] = ids[dma_plan[k] >> 16];      // all LDS reads before the first (ordering) asm statement
+#pragma unroll
+            for (int k = 0; k < SP_DMA_PER_WAVE; ++k)
+                glds16(prec_bytes + (size_t)(uint32_t)max(id[k], 0) * (SP_REC * 16) + (dma_plan[k] & 0xffffu), dst + (uint32_t)k * 1024u);
+        };
+
+        // best[iq]: best exact value this lane has produced for the current object; shared[iq]: the best anybody has published
+        float best[SP_NQ], shared[SP_NQ];
+        uint32_t grow[SP_NQ];                          // grow: word index of (pixel, object 0) in gbest (pixel 0 for rows past the end)
+#pragma unroll
+        for (int iq = 0; iq < SP_NQ; ++iq) {
+            grow[iq] = valid[iq] ? (uint32_t)(wave_row0 + iq * 32 + col) * (uint32_t)n_obj : 0u;
+            best[iq] = INFINITY;
+            shared[iq] = INFINITY;
+        }
+        int cur = -1;
+        // what the other workgroups have published for the current object: one 4-byte transfer per query tile into this wave's own LDS
+        // words, read back one step later (device-scope load: the values come from L2, not from this CU's vector cache)
+        auto dma_bound = [&]() {
 #pragma unroll
             for (int iq = 0; iq < SP_NQ; ++iq) {
-                const float cm = max16(acc[iq]);
-                want[iq] = __builtin_amdgcn_ballot_w64(cm + eps[iq] >= __builtin_fmaxf(best[iq], shared[iq])) != 0ull;
+                unsigned keep;
+                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off sc1\n\ts_mov_b32 m0, %0"
+                             : "=&s"(keep) : "v"(gbest + grow[iq] + max(cur, 0)), "s"(lds_base + SP_BND_OFF + (uint32_t)(wave * SP_NQ + iq) * 256u) : "memory");
             }
-            n_seen += 1;
-            if (want[0] || want[1]) {
-                n_any += 1;
-                // the tile's lo plane comes from the records in global memory (L2 / Infinity Cache resident: every workgroup of the
-                // split streams the same tiles), once per tile for both query tiles -- seven 16-byte loads per lane, row = the CURRENT chunk's id
-                // (slot s % 3 of the id ring; dma_meta(s + 2) and dma_rows(s + 1) use the other two slots during this step) -- and is waited for
-                // right here with an explicit vmcnt(0).  Outstanding at that point: the seven loads; in front of them this step's LDS-DMA statements
-                // (2 bounds, up to 2 meta, 7 rows: asm that hipcc does not count) unless an earlier tile of the step has drained them already, and
-                // fire-and-forget atomics of earlier rescorings.  vmcnt retires in issue order, so any wait for the loads covers all of these:
-                // correct, and a rescoring early in a step waits for the next chunk to land as well (the end of the step waits for it anyway).  No
-                // LDS-DMA is issued between the loads and their use.  Why not hipcc's own counted waits in front of each MFMA (vmcnt(6) ... (0)): the
-                // two rescorings are separate branches, its wait insertion merges the paths behind them, cannot know that one of the two always
-                // runs, keeps the loads pending around the tile loop and drains vmcnt(0) -- i.e. this step's DMA -- in front of EVERY tile's
-                // decision.  The explicit wait costs a rescoring tile the ~100 cycles of the first LDS read and MFMA that could have overlapped.
-                // Register arrays are indexed by unrolled constants only.
-                f16x8 alg[SP_KS];
-                auto load_lo = [&]() {
-                    const int id = ids_now[t * SP_TILE + col];
-                    const uint4 *lo = reinterpret_cast<const uint4 *>(prec_bytes + (size_t)(uint32_t)max(id, 0) * (SP_REC * 16) + SP_HALF * 16) + h;
+        };
+        auto switch_object = [&](int o) {
+            cur = o;
+            uint32_t u[SP_NQ];
 #pragma unroll
-                    for (int kk = 0; kk < SP_KS; ++kk) alg[kk] = __builtin_bit_cast(f16x8, lo[2 * ks_of(kk)]);
-                    __builtin_amdgcn_s_waitcnt(0x0f70);                 // vmcnt(0)
-                };
-                auto rescore = [&](auto iq_c) {
-                    constexpr int iq = decltype(iq_c)::value;
-                    // cross terms: acc += rh.ql + rl.qh (one chain of 14 MFMAs), then the exact maximum
-                    n_rescored += 1;
-                    f16x8 ah[3];
+            for (int iq = 0; iq < SP_NQ; ++iq) u[iq] = load_relaxed(gbest + grow[iq] + cur);
 #pragma unroll
-                    for (int kk = 0; kk < 2; ++kk) ah[kk] = frag(tile_base, 2 * ks_of(kk));
+            for (int iq = 0; iq < SP_NQ; ++iq) {
+                best[iq] = valid[iq] ? -INFINITY : INFINITY;         // rows past the end never ask for a rescoring
+                shared[iq] = valid[iq] ? ord_dec(u[iq]) : INFINITY;
+            }
+        };
+
+        // ---- prologue: meta of chunks 0 and 1, rows of chunk 0 (drained: once per workgroup)
+        dma_meta(0);
+        dma_meta(1);
+        __builtin_amdgcn_s_waitcnt(0x0f70);                           // vmcnt(0)
+        __builtin_amdgcn_s_barrier();
+        dma_rows(0);
+        __builtin_amdgcn_s_waitcnt(0x0f70);
+        __builtin_amdgcn_s_barrier();
+
+        // A fragment addressing: chunk index e + h (e even, compile time) of row (tile, col) sits at position (e & ~1) + (h ^ x),
+        // x = (col >> 3) & 1: one per-lane byte offset covers it
+        const int xs = (col >> 3) & SWZ_MASK;
+        const uint32_t row_off = (uint32_t)col * SP_ROW_BYTES;
+        const uint32_t sw0 = row_off + (uint32_t)((h ^ xs) * 16), sw2 = sw0 + 32u;
+        auto frag = [&](const char *tile_base, int e) -> f16x8 {       // e: even chunk index (2 ks)
+            const uint32_t off = ((e & 2) ? sw2 : sw0) + (uint32_t)((e & ~3) * 16);
+            return __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4 *>(tile_base + off));
+        };
+        auto ks_of = [&](int kk) { return (kk + SP_KS - 1) % SP_KS; };  // norm slots first: partial sums stay small
+
+        for (int s = 0; s < n_chunks; ++s) {
+            // (a) prefetches for the next step: published bounds of the current object, meta of chunk s + 2, rows of chunk s + 1 (whose ids
+            // the barrier that ended step s - 1 published)
+            const int4 objs = *reinterpret_cast<const int4 *>(lds_bytes + SP_OBJ_OFF + (s & 3) * 256);
+            const int4 objs_b = *reinterpret_cast<const int4 *>(lds_bytes + (s & 3) * 256 + SP_OBJ_OFF + 16);      // tiles 4..7
+            const int bound_obj = cur;
+            dma_bound();
+            dma_meta(s + 2);
+            dma_rows(s + 1);
+
+            // (b) the eight tiles of chunk s
+            const char *chunk_base = lds_bytes + (s % SP_NBUF) * SP_CHUNK_BYTES;
+            const int n_here = min(SP_NB_HI, n_mine - s * SP_NB_HI);
+            // the first two A fragments of a tile are requested while the previous tile's epilogue runs
+            f16x8 pre0 = frag(chunk_base, 2 * ks_of(0)), pre1 = frag(chunk_base, 2 * ks_of(1));
+            // the tiles' objects in one 64-bit scalar (objects are < 256): two SALU operations per tile instead of a chain of selects
+            const uint32_t objs_lo = (uint32_t)__builtin_amdgcn_readfirstlane((objs.x & 0xff) | ((objs.y & 0xff) << 8) | ((objs.z & 0xff) << 16) | ((objs.w & 0xff) << 24));
+            const uint32_t objs_hi = (uint32_t)__builtin_amdgcn_readfirstlane((objs_b.x & 0xff) | ((objs_b.y & 0xff) << 8) | ((objs_b.z & 0xff) << 16) | ((objs_b.w & 0xff) << 24));
+            const uint64_t objs_packed = ((uint64_t)objs_hi << 32) | objs_lo;
+            // the current chunk's row ids (the rescoring path addresses the lo planes in global memory with them)
+            const int32_t *ids_now = reinterpret_cast<const int32_t *>(lds_bytes + SP_IDS_OFF + (s % SP_IDS_SLOTS) * SP_IDS_SLOT_BYTES);
+#pragma unroll 1
+            for (int t = 0; t < n_here; ++t) {
+                const char *tile_base = chunk_base + t * SP_TILE_BYTES;
+                const int o = (int)((objs_packed >> (8 * t)) & 0xffu);
+                if (o != cur) switch_object(o);
+                // coarse pass: 7 k-steps x 2 query tiles, A fragments two k-steps ahead through a ring of three
+                f32x16 acc[SP_NQ];
+#pragma unroll
+                for (int iq = 0; iq < SP_NQ; ++iq)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[iq][r] = 0.0f;
+                {
+                    f16x8 af[3];
+                    af[0] = pre0;
+                    af[1] = pre1;
 #pragma unroll
                     for (int kk = 0; kk < SP_KS; ++kk) {
-                        if (kk + 2 < SP_KS) ah[(kk + 2) % 3] = frag(tile_base, 2 * ks_of(kk + 2));
-                        acc[iq] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[kk % 3], bl[iq][ks_of(kk)], acc[iq], 0, 0, 0);
-                        acc[iq] = __builtin_amdgcn_mfma_f32_32x32x16_f16(alg[kk], bh[iq][ks_of(kk)], acc[iq], 0, 0, 0);
-                    }
-                    const float ex = max16(acc[iq]);
-                    if (ex > best[iq]) {
-                        best[iq] = ex;
-                        if (ex > shared[iq]) atomicMax(gbest + grow[iq] + cur, ord_enc(ex));      // fire and forget
-                    }
-                };
-                load_lo();
-                if (want[0]) rescore(std::integral_constant<int, 0>{});
-                if (want[1]) rescore(std::integral_constant<int, 1>{});
-            }
-        }
-
-        // (c) this step's transfers have landed (they had the step's tiles of time).  The wave reads back its own bound words right away (its
-        // own vmcnt(0) covers them) so that the lgkmcnt(0) below also retires those reads before the next step's transfer can overwrite
-        // the words; then the barrier publishes the chunk and the row ids to the other waves.
-        __builtin_amdgcn_s_waitcnt(0x0f70);          // vmcnt(0)
-        uint32_t seen[SP_NQ];
+                        if (kk + 2 < SP_KS) af[(kk + 2) % 3] = frag(tile_base, 2 * ks_of(kk + 2));
 #pragma unroll
-        for (int iq = 0; iq < SP_NQ; ++iq)
-            seen[iq] = *reinterpret_cast<const volatile uint32_t *>(lds_bytes + SP_BND_OFF + (wave * SP_NQ + iq) * 256 + lane * 4);
-        __builtin_amdgcn_s_waitcnt(0xc07f);          // lgkmcnt(0)
-        __builtin_amdgcn_s_barrier();
-        if (bound_obj == cur && cur >= 0) {
+                        for (int iq = 0; iq < SP_NQ; ++iq)
+                            acc[iq] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[kk % 3], bh[iq][ks_of(kk)], acc[iq], 0, 0, 0);
+                    }
+                    if (t + 1 < n_here) {
+                        pre0 = frag(tile_base + SP_TILE_BYTES, 2 * ks_of(0));
+                        pre1 = frag(tile_base + SP_TILE_BYTES, 2 * ks_of(1));
+                    }
+                }
+                // which query tiles may hold a new maximum (wave-uniform)
+                bool want[SP_NQ];
+#pragma unroll
+                for (int iq = 0; iq < SP_NQ; ++iq) {
+                    const float cm = max16(acc[iq]);
+                    want[iq] = __builtin_amdgcn_ballot_w64(cm + eps[iq] >= __builtin_fmaxf(best[iq], shared[iq])) != 0ull;
+                }
+                n_seen += 1;
+                if (want[0] || want[1]) {
+                    n_any += 1;
+                    // the tile's lo plane comes from the records in global memory (L2 / Infinity Cache resident: every workgroup of the
+                    // split streams the same tiles), once per tile for both query tiles -- seven 16-byte loads per lane, row = the CURRENT chunk's id
+                    // (slot s % 3 of the id ring; dma_meta(s + 2) and dma_rows(s + 1) use the other two slots during this step) -- and is waited for
+                    // right here with an explicit vmcnt(0).  Outstanding at that point: the seven loads; in front of them this step's LDS-DMA statements
+                    // (2 bounds, up to 2 meta, 7 rows: asm that hipcc does not count) unless an earlier tile of the step has drained them already, and
+                    // fire-and-forget atomics of earlier rescorings.  vmcnt retires in issue order, so any wait for the loads covers all of these:
+                    // correct, and a rescoring early in a step waits for the next chunk to land as well (the end of the step waits for it anyway).  No
+                    // LDS-DMA is issued between the loads and their use.  Why not hipcc's own counted waits in front of each MFMA (vmcnt(6) ... (0)): the
+                    // two rescorings are separate branches, its wait insertion merges the paths behind them, cannot know that one of the two always
+                    // runs, keeps the loads pending around the tile loop and drains vmcnt(0) -- i.e. this step's DMA -- in front of EVERY tile's
+                    // decision.  The explicit wait costs a rescoring tile the ~100 cycles of the first LDS read and MFMA that could have overlapped.
+                    // Register arrays are indexed by unrolled constants only.
+                    f16x8 alg[SP_KS];
+                    auto load_lo = [&]() {
+                        const int id = ids_now[t * SP_TILE + col];
+                        const uint4 *lo = reinterpret_cast<const uint4 *>(prec_bytes + (size_t)(uint32_t)max(id, 0) * (SP_REC * 16) + SP_HALF * 16) + h;
+#pragma unroll
+                        for (int kk = 0; kk < SP_KS; ++kk) alg[kk] = __builtin_bit_cast(f16x8, lo[2 * ks_of(kk)]);
+                        __builtin_amdgcn_s_waitcnt(0x0f70);                 // vmcnt(0)
+                    };
+                    auto rescore = [&](auto iq_c) {
+                        constexpr int iq = decltype(iq_c)::value;
+                        // cross terms: acc += rh.ql + rl.qh (one chain of 14 MFMAs), then the exact maximum
+                        n_rescored += 1;
+                        f16x8 ah[3];
+#pragma unroll
+                        for (int kk = 0; kk < 2; ++kk) ah[kk] = frag(tile_base, 2 * ks_of(kk));
+#pragma unroll
+                        for (int kk = 0; kk < SP_KS; ++kk) {
+                            if (kk + 2 < SP_KS) ah[(kk + 2) % 3] = frag(tile_base, 2 * ks_of(kk + 2));
+                            acc[iq] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[kk % 3], bl[iq][ks_of(kk)], acc[iq], 0, 0, 0);
+                            acc[iq] = __builtin_amdgcn_mfma_f32_32x32x16_f16(alg[kk], bh[iq][ks_of(kk)], acc[iq], 0, 0, 0);
+                        }
+                        const float ex = max16(acc[iq]);
+                        if (ex > best[iq]) {
+                            best[iq] = ex;
+                            if (ex > shared[iq]) atomicMax(gbest + grow[iq] + cur, ord_enc(ex));      // fire and forget
+                        }
+                    };
+                    load_lo();
+                    if (want[0]) rescore(std::integral_constant<int, 0>{});
+                    if (want[1]) rescore(std::integral_constant<int, 1>{});
+                }
+            }
+
+            // (c) this step's transfers have landed (they had the step's tiles of time).  The wave reads back its own bound words right away (its
+            // own vmcnt(0) covers them) so that the lgkmcnt(0) below also retires those reads before the next step's transfer can overwrite
+            // the words; then the barrier publishes the chunk and the row ids to the other waves.
+            __builtin_amdgcn_s_waitcnt(0x0f70);          // vmcnt(0)
+            uint32_t seen[SP_NQ];
 #pragma unroll
             for (int iq = 0; iq < SP_NQ; ++iq)
-                if (valid[iq]) shared[iq] = __builtin_fmaxf(shared[iq], ord_dec(seen[iq]));
+                seen[iq] = *reinterpret_cast<const volatile uint32_t *>(lds_bytes + SP_BND_OFF + (wave * SP_NQ + iq) * 256 + lane * 4);
+            __builtin_amdgcn_s_waitcnt(0xc07f);          // lgkmcnt(0)
+            __builtin_amdgcn_s_barrier();
+            if (bound_obj == cur && cur >= 0) {
+#pragma unroll
+                for (int iq = 0; iq < SP_NQ; ++iq)
+                    if (valid[iq]) shared[iq] = __builtin_fmaxf(shared[iq], ord_dec(seen[iq]));
+            }
         }
+        // Between items nothing more is needed: every wave drained its own transfers (vmcnt(0)) and finished its LDS reads (the tiles of the last
+        // chunk, its bound words: lgkmcnt(0)) before the barrier that ended the last step, so behind that barrier no transfer is in flight and no
+        // wave reads the ring, the id / object slots or the bound words, and the next item's prologue may overwrite them.
     }
-    if (lane == 0) {
+    if (aoc_lane() == 0) {
         atomicAdd(&g_prune_stats[0], (unsigned long long)n_seen * SP_NQ);
         atomicAdd(&g_prune_stats[1], (unsigned long long)n_rescored);
         atomicAdd(&g_prune_stats[2], (unsigned long long)n_any);
@@ -694,25 +709,41 @@ __global__ void split_gate_refresh_kernel(const int32_t *__restrict__ overflow, 
     if (*overflow) atomicOr(gate, 1);
 }
 
-inline int split_nsplit(int64_t m) {
+// The share of the stream's CUs that dense_prune_kernel's resident workgroups take, in 256ths (aoc_set_dense_share).  The rest of the CUs stays
+// free for the kernels of other streams (the gates and the front end of the other sequence in flight) for the whole dense launch.
+std::atomic<int> g_dense_share{AOC_DENSE_SHARE_DEFAULT};
+
+struct SplitSizing {
+    int splits, items, workgroups;
+};
+// budget: CUs the launching stream may use (0 = 256: no CU mask); share: 1 .. 256.
+inline SplitSizing split_sizing(int64_t m, int budget, int share) {
     const int64_t row_blocks = (m + SP_ROWS_PER_BLOCK - 1) / SP_ROWS_PER_BLOCK;
-    // at most two rounds of workgroups: fewer splits share their bounds sooner (in-run launch 1.43 / 1.50 / 1.56 ms at 1 / 2 / 4 rounds),
-    // but with one round the other streams' kernels wait for a whole dense launch before a CU comes free: bench 320 / 324 / 320 frames/s
-    constexpr int max_rounds = 2;
-    // CUs the launching stream may use (256 unless the caller runs it under a HIP CU mask and says so): one resident workgroup each
-    const int n_cu = aoc_stream_cus() > 0 ? aoc_stream_cus() : 256;
+    const int n_cu = budget > 0 ? budget : 256;
+    // resident workgroups, one per CU: the share of the budget, a multiple of 8 from 8 up (the kernel's XCD map), at least one
+    int64_t g = ((int64_t)n_cu * share) >> 8;
+    if (g >= 8) g &= ~(int64_t)7;
+    if (g < 1) g = 1;
+    // The split count fills whole rounds of g.  Fewer splits share their bounds sooner (in-run launch 1.43 / 1.50 / 1.56 ms at 1 / 2 / 4 rounds of
+    // the whole budget), more rounds leave a shorter ragged end.  At the whole budget (share 256) the rule is the one the one-workgroup-per-item
+    // kernel was sized by, two rounds at most: the same splits as before.  A smaller g may take a third round, which keeps the splits near those of
+    // the whole budget (51 row blocks on 224 CUs: 8 splits; on 136: 8 splits in three full rounds).
+    const int max_rounds = share >= 256 ? 2 : 3;
     int best = 1;
     double best_eff = 0.0;
     for (int k = 1; k <= max_rounds; ++k) {
-        int64_t ns = ((int64_t)n_cu * k) / row_blocks;
+        int64_t ns = (g * k) / row_blocks;
         if (ns < 1) ns = 1;
         if (ns > 64) ns = 64;
         const int64_t blocks = row_blocks * ns;
-        const int64_t rounds = (blocks + n_cu - 1) / n_cu;
-        const double eff = (double)blocks / ((double)n_cu * rounds);
+        const int64_t rounds = (blocks + g - 1) / g;
+        const double eff = (double)blocks / ((double)g * rounds);
         if (eff >= best_eff - 0.005) { best_eff = eff > best_eff ? eff : best_eff; best = (int)ns; }
     }
-    return best;
+    const int64_t items = row_blocks * best;
+    if (g > items) g = items;
+    if (g >= 8) g &= ~(int64_t)7;
+    return SplitSizing{best, (int)items, (int)g};
 }
 
 struct SplitWs {
@@ -816,14 +847,16 @@ int aoc_dense_match_min_split_cached(const float *query, const void *query_rec, 
     if (n >= m)
         hipLaunchKernelGGL(dense_seed_kernel, dim3((unsigned)((m * 8 + 255) / 256)), dim3(256), 0, st, query, query_sqnorm, m, C, pool, n, right_bits, n_obj, w.gate,
                            w.gbest);
-    const dim3 grid((unsigned)((m + SP_ROWS_PER_BLOCK - 1) / SP_ROWS_PER_BLOCK), split_nsplit(m));
+    const SplitSizing sz = split_sizing(m, aoc_stream_cus(), g_dense_share.load(std::memory_order_relaxed));
+    const dim3 grid((unsigned)sz.workgroups);
     const AocDenseProbe probe = aoc_take_dense_probe();
     static const bool lds_ok = hipFuncSetAttribute(reinterpret_cast<const void *>(dense_prune_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                    SP_LDS_BYTES) == hipSuccess;
     if (!lds_ok) return AOC_ERR_LAUNCH;
     if (probe.start) (void)hipEventRecord(probe.start, st);
     hipLaunchKernelGGL(dense_prune_kernel<0>, grid, dim3(SP_NW * 64), SP_LDS_BYTES, st, static_cast<const uint4 *>(query_rec), query_sqnorm, m,
-                       static_cast<const uint4 *>(pool_rec), w.tile_rows, w.tile_obj, w.n_tiles, w.gate, w.pmax, n_obj, w.gbest, query_rec_tiled ? 1 : 0);
+                       static_cast<const uint4 *>(pool_rec), w.tile_rows, w.tile_obj, w.n_tiles, w.gate, w.pmax, n_obj, w.gbest, query_rec_tiled ? 1 : 0,
+                       sz.splits);
     if (probe.stop) (void)hipEventRecord(probe.stop, st);
     hipLaunchKernelGGL(dense_split_finalize_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, w.gbest, m, n_obj, counts, w.gate,
                        query_sqnorm, obj_bias, out, out_pixel_stride, out_obj_stride, transform);
@@ -837,6 +870,22 @@ static std::atomic<int> g_stream_cus{0};
 int aoc_set_stream_cus(int n_cus) {
     if (n_cus < 0) return AOC_ERR_INVALID_ARG;
     g_stream_cus.store(n_cus, std::memory_order_relaxed);
+    return AOC_OK;
+}
+
+int aoc_set_dense_share(int share_256) {
+    if (share_256 < 1 || share_256 > 256) return AOC_ERR_INVALID_ARG;
+    g_dense_share.store(share_256, std::memory_order_relaxed);
+    return AOC_OK;
+}
+int aoc_dense_share(void) { return g_dense_share.load(std::memory_order_relaxed); }
+
+int aoc_dense_split_sizing(int64_t m, int budget, int share_256, int32_t *splits, int32_t *items, int32_t *workgroups) {
+    if (m < 1 || m >= (1ll << 31) || budget < 0 || share_256 < 1 || share_256 > 256 || !splits || !items || !workgroups) return AOC_ERR_INVALID_ARG;
+    const SplitSizing sz = split_sizing(m, budget, share_256);
+    *splits = sz.splits;
+    *items = sz.items;
+    *workgroups = sz.workgroups;
     return AOC_OK;
 }
 

@@ -707,10 +707,17 @@ def dense_match_min_split(query_flat, query_split, pool, pool_split, prep, obj_b
 DENSE_PRECISION = os.environ.get("AOC_DENSE_PRECISION", "split")
 
 
-def set_stream_cus(n_cus):
+def set_stream_cus(n_cus=None, dense_share=None):
     """aoc_set_stream_cus: how many CUs the streams that launch the matrix kernels may use (a caller that runs them under a HIP CU mask
-    says so; 0 = every CU of the device)."""
-    _lib.check(_lib.lib().aoc_set_stream_cus(int(n_cus)), "aoc_set_stream_cus")
+    says so; 0 = every CU of the device).  dense_share (aoc_set_dense_share): the share of those CUs, in 256ths (1 .. 256), that the dense
+    matching kernel's resident workgroups take; the rest stays free for other streams.  None leaves a value as it is.
+    -> the dense share now in force (aoc_dense_share)."""
+    L = _lib.lib()
+    if n_cus is not None:
+        _lib.check(L.aoc_set_stream_cus(int(n_cus)), "aoc_set_stream_cus")
+    if dense_share is not None:
+        _lib.check(L.aoc_set_dense_share(int(dense_share)), "aoc_set_dense_share")
+    return int(L.aoc_dense_share())
 
 
 def dense_match(query_flat, pool, prep, obj_bias, out, out_pixel_stride, out_obj_stride, transform=True, precision=None,
