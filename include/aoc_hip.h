@@ -1346,6 +1346,45 @@ int aoc_criterion_forward(const float *pred, const int32_t *labels, int C, int h
 int aoc_upsample_ce_grad(const float *pred, const int32_t *labels, const float *lse, const uint8_t *mask, const float *grad_out, int64_t k,
                          const int32_t *n_valid, int C, int h, int w, int H, int W, int ignore_index, float *grad_pred, aoc_stream_t stream);
 
+/*
+ * Training-time DynamicPreHead (csrc/prehead_grad.hip; aoc_amd.prehead_train): the backward of aoc_prehead, i.e. of decoding_module.py:228-240
+ * (`x = self.conv(x); x = self.bn(x); x = self.relu(x)`) with the concatenation of aocnet.py:360-362 (`pre_to_cat = self.dynamic_prehead(
+ * pre_to_cat)`, `torch.cat((to_cat_current_frame_embedding, pre_to_cat), 1)`, the embedding expanded over the objects at aocnet.py:188).
+ * fp32, no float atomics, every sum in an order fixed by the shapes alone (no pointer alignment enters); two runs on the same buffers give the
+ * same bits.  The limits and their status codes are aoc_prehead's: n_in <= 32, n_out <= 128, n_out % n_groups == 0, n_obj <= 65535, and an
+ * embedding pointer that contradicts C (here: grad_emb_hwc != NULL with C == 0) -> AOC_ERR_UNSUPPORTED; a NULL required pointer or a
+ * non-positive size -> AOC_ERR_INVALID_ARG; a short workspace -> AOC_ERR_WORKSPACE.  The grids add hw <= 2^37 and C <= 65535 * 32 (beyond:
+ * AOC_ERR_UNSUPPORTED).  A rejected call enqueues nothing.
+ *
+ * grad_out [n_obj, C + n_out, hw] is the cotangent of aoc_prehead's out; feat [n_obj, n_in, hw] its input; stats [n_obj * n_groups][2] the
+ * float32 (mean, rstd) aoc_prehead left in its workspace (behind n_obj * n_groups * n_chunks * 16 bytes rounded up to a multiple of 256,
+ * n_chunks = ceil(hw / 256)); weight [n_out, n_in], bias, gamma, beta [n_out].  For object o, channel c of group g, pixel p, M = (n_out / n_groups) * hw:
+ *   y    = fmaf(w[c,n_in-1], x[n_in-1], ... fmaf(w[c,0], x[0], bias[c]))           aoc_prehead's chain: bias first, k ascending
+ *   xhat = (y - mean) * rstd          v = xhat * gamma[c] + beta[c]                aoc_prehead's own expression, one rounding per operation
+ *   dz   = grad_out[o, C + c, p] where v > 0, else 0.0f                            (a select: the forward output's own `> 0`, bit for bit)
+ *   SA[o,c] = sum_p dz                SB[o,c] = sum_p fl(dz * xhat)                in double: per chunk of 256 pixels eight runs (run j: the pixels
+ *                                                                                  4 (j + 8 m) .. + 3, m = 0 .. 7, ascending), the eight by xor butterfly
+ *                                                                                  (4, 2, 1); then the chunks, dealt to 64 sums (sum l: the chunks l,
+ *                                                                                  l + 64, ... ascending), the 64 by xor butterfly (32 .. 1)
+ *   grad_beta[c]  = (float) sum_o SA[o,c]       grad_gamma[c] = (float) sum_o SB[o,c]             double, the (object, chunk) pairs dealt to 64 sums likewise
+ *   c1[o,g] = (float)(sum_{c in g} (double)gamma[c] * SA[o,c] / M)      c2[o,g] likewise from SB  double, c ascending from 0.0; M as a double
+ *   dy   = rstd * ((gamma[c] * dz - c1) - xhat * c2)                               float32, one rounding per operation
+ *   grad_feat[o,k,p] = fmaf(w[n_out-1,k], dy_{n_out-1}, ... fmaf(w[0,k], dy_0, 0.0f))             c ascending
+ *   P[o,chunk,c,k]   = fmaf(dy_p, x_k[p], ...) over the chunk's 256 pixels, p ascending from 0.0f; P[o,chunk,c,n_in] the same with x = 1.0f
+ *   grad_weight[c,k] = (float) sum_{o,chunk} (double)P[o,chunk,c,k]     grad_bias[c] = (float) sum_{o,chunk} (double)P[o,chunk,c,n_in]
+ *                      double; the (object, chunk) pairs i = 0, 1, ... dealt to four sums s = i mod 4, each ascending, then ((s0 + s1) + s2) + s3
+ *   grad_emb_hwc[p,k] = sum_o grad_out[o,k,p]                                      float32, o ascending from 0.0f
+ * Every output is optional (NULL: its work is skipped) and has the same bits alone as with the others: the plane pass and the traversal do
+ * not depend on what is asked for.  grad_emb_hwc [hw, C] is channel-last like emb_hwc and must be NULL when C == 0.  No mask, y, xhat or dy
+ * tensor is stored: five launches (plane pass, the small sums, apply pass, the reduction of P, the embedding's transposing sum) read the
+ * n_out channels of grad_out and feat twice and the embedding's channels once.  The workspace holds SA / SB per chunk, (c1, c2) and P
+ * (n_obj * n_chunks * n_out * (n_in + 1) floats); it is needed unless grad_emb_hwc is the only output. */
+size_t aoc_prehead_grad_workspace_bytes(int n_obj, int n_in, int n_out, int n_groups, int64_t hw);
+int aoc_prehead_grad(const float *grad_out, const float *feat, const float *stats, const float *weight, const float *bias, const float *gamma,
+                     const float *beta, int n_obj, int n_in, int n_out, int n_groups, int64_t hw, int C, float *grad_feat, float *grad_weight,
+                     float *grad_bias, float *grad_gamma, float *grad_beta, float *grad_emb_hwc, void *workspace, size_t workspace_bytes,
+                     aoc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

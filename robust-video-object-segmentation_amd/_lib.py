@@ -175,6 +175,8 @@ SIGNATURES = {
     "aoc_criterion_forward_workspace_bytes": (_sz, [_i64]),
     "aoc_criterion_forward": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "aoc_upsample_ce_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "aoc_prehead_grad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i64]),
+    "aoc_prehead_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 STATUS = {0: "AOC_OK", -1: "AOC_ERR_INVALID_ARG", -2: "AOC_ERR_WORKSPACE", -3: "AOC_ERR_LAUNCH", -4: "AOC_ERR_UNSUPPORTED"}

@@ -46,7 +46,8 @@ _TRAINABLE = {"global_matching_for_eval": "matching_train.global_matching", "glo
               "Bottleneck": "decoder_train.Bottleneck", "M1": "decoder_train.Modulator_1", "M2": "decoder_train.Modulator_2",
               "decoder_final": "tail_train.decoder_final", "predict": "tail_train.predict",
               "augment_background_logit": "tail_train.augment_background_logit",
-              "ASPP": "aspp_train.ASPP", "_ASPPModule": "aspp_train._ASPPModule"}
+              "ASPP": "aspp_train.ASPP", "_ASPPModule": "aspp_train._ASPPModule",
+              "DynamicPreHead": "prehead_train.DynamicPreHead"}
 
 
 def inference_only(what, *tensors):
@@ -56,7 +57,7 @@ def inference_only(what, *tensors):
     have a backward live in aoc_amd.matching_train (global_matching, global_matching_proxy), aoc_amd.local_train (local_matching,
     local_matching_proxy), aoc_amd.cluster_train (global_matching_cluster2), aoc_amd.frontend_train (foreground2background, the attention
     heads, the aggregation), aoc_amd.gates_train (IA_gate, GCT, conditioning_layer, conditioning_block), aoc_amd.decoder_train (Bottleneck,
-    Modulator_1, Modulator_2), aoc_amd.tail_train (decoder_final, predict, augment_background_logit) and aoc_amd.aspp_train (ASPP, _ASPPModule);
+    Modulator_1, Modulator_2), aoc_amd.tail_train (decoder_final, predict, augment_background_logit), aoc_amd.aspp_train (ASPP, _ASPPModule) and aoc_amd.prehead_train (DynamicPreHead);
     the error text says so for them."""
     if torch.is_grad_enabled():
         for t in tensors:
