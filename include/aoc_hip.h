@@ -28,6 +28,48 @@
  *   - aoc_dense_match_min_split_cached with reuse_plan != 0: the workspace holds what the last reuse_plan = 0 call for the same pool
  *     state and the same m left there, and nothing else has written to it since;
  *   - aoc_frame_enqueue: the workspace's content is described by the caller's aoc_seq_state; a zeroed state record goes with any content.
+ *
+ * Pointer alignment (label prep, k-means, proxy build, correlation, dense and local matching and their gradients, the frame and chain calls;
+ * the entries further down state theirs in their own comments)
+ *  Every device pointer is at least 4-byte aligned (float / int32 elements).  A pointer is CLASS 16 when some kernel reaches it through a
+ *  16-byte access -- float4 / uint4 loads or stores, a 16-byte buffer load, an LDS-direct global_load_lds_dwordx4 -- or when it is an opaque
+ *  record buffer of aoc_split_rows[_tiled]: it must lie on the 16-byte grid, and the entry returns AOC_ERR_INVALID_ARG for one that does
+ *  not, BEFORE it enqueues or writes anything (host code: no kernel ever sees such a pointer).  With C a multiple of 4 every row of an
+ *  aligned [*, C] table is aligned again, so pool prefixes, ref_emb[r] and table row ranges keep the class.  Every other pointer is CLASS 4:
+ *  the kernels read and write it with 4-byte accesses only, and it may sit at any float boundary -- labels and bit masks, row lists,
+ *  counts (counts + n_obj is what the library itself passes as n_fg), norms, biases, every `out` addressed with strides (a channel slice of
+ *  the proto-mask tensor at odd hw), gradients.  No class-4 pointer's alignment enters a summation order: results do not depend on where
+ *  it sits, bit for bit (tests/test_gpu_alignment.py).  HOST arrays and descriptors (*_host, frames_host, desc, state, tables_key) are read by
+ *  the host code with their natural alignment; the classes of the pointers inside a descriptor are listed under the structure's name.
+ *  tests/alignment_cases.py holds this table as data, with the source line behind every class-16 entry.  Class-16 pointers per entry
+ *  (every pointer parameter not named is class 4; "-" = none):
+ *   aoc_label_prep / aoc_label_bits                                         16: -
+ *   aoc_kmeans_segmented / aoc_kmeans_segmented_ex / aoc_kmeans_segmented_rep   16: pool, centroids, workspace
+ *   aoc_kmeans_replicate / aoc_kmeans_replicate_levels                      16: -
+ *   aoc_build_proxies                                                       16: pool, workspace
+ *   aoc_proxy_corr_min / aoc_proxy_corr_min_f16                             16: proxies
+ *   aoc_proxy_corr_min_batched / aoc_proxy_corr_min_records                 16: -
+ *   aoc_proxy_corr_min_records_cached                                       16: workspace
+ *   aoc_corr_frame                                                          16: query, proxies
+ *   aoc_corr_frame_rec                                                      16: query_rec, proxies
+ *   aoc_dense_match_min / aoc_dense_match_min_f16 / aoc_dense_match_argmin  16: pool
+ *   aoc_split_rows / aoc_split_rows_tiled                                   16: x, records
+ *   aoc_dense_match_min_split / aoc_dense_match_min_split_cached            16: query, query_rec, pool, pool_rec, workspace
+ *   aoc_dense_match_grad / aoc_proxy_match_grad                             16: -
+ *   aoc_local_window_match / aoc_local_window_match_ex / aoc_local_window_match_argmin   16: query, prev
+ *   aoc_local_window_match_pair                                             16: query, prev_a, prev_b
+ *   aoc_local_match_grad / aoc_local_prep                                   16: -
+ *   aoc_resize_bilinear_hwc / aoc_resize_bilinear_hwc_ex / aoc_resize_nearest_bits   16: -
+ *   aoc_atrous_subsample                                                    16: in, out
+ *   aoc_proxy_set_match_argmin / aoc_proxy_set_match_grad / aoc_centroid_avg_grad   16: -
+ *   aoc_proto_finish / aoc_fg2bg_min                                        16: -
+ *   aoc_frame_enqueue / aoc_cluster_chain_enqueue                           16: workspace
+ *   aoc_frame_desc                                                          16: ref_emb, match_emb, prev_emb, cur_emb, proxy_table
+ *   aoc_chain_desc                                                          16: pool, tables
+ *  Two classes are conditional.  aoc_atrous_subsample: the class holds for X % 4 == 0, the one case that moves 16 bytes per thread; for every
+ *  other X both pointers are class 4 and the entry accepts them anywhere.  aoc_proxy_corr_min_records_cached: the workspace is class 16 when
+ *  tables_key != NULL (only then does it hold the tile tables, which have 8-byte members); with a NULL key the call is
+ *  aoc_proxy_corr_min_records and the workspace class 4.  Each covered prototype below repeats its own line of this list.
  */
 #ifndef AOC_HIP_H
 #define AOC_HIP_H
@@ -74,6 +116,7 @@ const char *aoc_version(void);
  *  obj_offsets [n_obj + 1] out: exclusive prefix sum of counts[0..n_obj)
  */
 size_t aoc_label_prep_workspace_bytes(int64_t n, int n_obj);
+/* Alignment ("Pointer alignment" above): class 16: -; every other pointer class 4. */
 int aoc_label_prep(const float *labels, int64_t n, int n_obj,
                    uint32_t *right_bits, uint32_t *wrong_bits,
                    int32_t *fg_rows, int32_t *obj_rows,
@@ -82,6 +125,7 @@ int aoc_label_prep(const float *labels, int64_t n, int n_obj,
 
 /* Bit masks only (same definition as above; wrong_bits may be NULL).  Used by local matching
  * (AEM:1023-1028: label > 0.9 of the previous frame). */
+/* Alignment ("Pointer alignment" above): class 16: -; every other pointer class 4. */
 int aoc_label_bits(const float *labels, int64_t n, int n_obj, uint32_t *right_bits,
                    uint32_t *wrong_bits, aoc_stream_t stream);
 
@@ -104,6 +148,7 @@ int aoc_kmeans_init_rows_draw(uint32_t *mt_key, int32_t *mt_pos, const int32_t *
  * eval_manager_mm.py:356-361) can then advance together in one aoc_kmeans_segmented_ex call with n_rep * n_seg segments.
  * rows_out [n_rep * rows_capacity], seg_offsets_out [n_rep * n_seg + 1], seg_k_out [n_rep * n_seg]; replica f's segment s
  * is rows_out[seg_offsets_out[f * n_seg + s] ...).  Device-side (the segment sizes never reach the host). */
+/* Alignment ("Pointer alignment" above): class 16: -; every other pointer class 4. */
 int aoc_kmeans_replicate(const int32_t *rows, const int32_t *seg_offsets, const int32_t *seg_k, int n_seg, int n_rep,
                          int64_t rows_capacity, int32_t *rows_out, int32_t *seg_offsets_out, int32_t *seg_k_out,
                          aoc_stream_t stream);
@@ -113,6 +158,7 @@ int aoc_kmeans_replicate(const int32_t *rows, const int32_t *seg_offsets, const 
  * K in {8, 16, 32}; the reference's `cluster_num` argument, AEM:231-232, one call per level): n_rep = frames x levels replicas
  * advance in ONE aoc_kmeans_segmented_ex chain with kmax = max level.  n_levels <= 8.  n_rep == 1 with rows_out == rows only
  * writes seg_offsets_out / seg_k_out. */
+/* Alignment ("Pointer alignment" above): class 16: -; every other pointer class 4. */
 int aoc_kmeans_replicate_levels(const int32_t *rows, const int32_t *seg_offsets, int n_seg, int n_rep,
                                 const int32_t *levels_host, int n_levels, int64_t rows_capacity, int32_t *rows_out,
                                 int32_t *seg_offsets_out, int32_t *seg_k_out, aoc_stream_t stream);
@@ -143,6 +189,7 @@ size_t aoc_kmeans_workspace_bytes(int64_t rows_capacity, int n_seg, int kmax, in
 /* Same, with the number of rows of `pool` stated (pool_rows > 0): enables the pipelined ordered
  * accumulation, which addresses rows through a bounds-checked buffer descriptor.  pool_rows = 0
  * (or aoc_kmeans_segmented) selects the generic path.  Results are bit-identical either way. */
+/* Alignment ("Pointer alignment" above): class 16: pool, centroids, workspace; every other pointer class 4. */
 int aoc_kmeans_segmented_ex(const float *pool, int64_t pool_rows, int C,
                             const int32_t *rows, const int32_t *seg_offsets, const int32_t *seg_k,
                             const int32_t *init_rows, int n_seg, int kmax, int iters,
@@ -154,12 +201,14 @@ int aoc_kmeans_segmented_ex(const float *pool, int64_t pool_rows, int C,
  * several frames that see one pool state (AEM:268-276, eval_manager_mm.py:356-361) and of the cluster levels of BASELINE.json configs[2]
  * in ONE chain; stating n_rep lets the assignment step fetch every pool row once per group of replicas instead of once per replica.
  * Results are bit-identical to n_rep = 1 (= aoc_kmeans_segmented_ex), which is always a valid way to run the same lists. */
+/* Alignment ("Pointer alignment" above): class 16: pool, centroids, workspace; every other pointer class 4. */
 int aoc_kmeans_segmented_rep(const float *pool, int64_t pool_rows, int C,
                              const int32_t *rows, const int32_t *seg_offsets, const int32_t *seg_k,
                              const int32_t *init_rows, int n_seg, int n_rep, int kmax, int iters,
                              int64_t rows_capacity,
                              float *centroids, int32_t *labels, int32_t *cluster_counts,
                              void *workspace, size_t workspace_bytes, aoc_stream_t stream);
+/* Alignment ("Pointer alignment" above): class 16: pool, centroids, workspace; every other pointer class 4. */
 int aoc_kmeans_segmented(const float *pool, int C,
                          const int32_t *rows, const int32_t *seg_offsets, const int32_t *seg_k,
                          const int32_t *init_rows, int n_seg, int kmax, int iters,
@@ -176,6 +225,7 @@ int aoc_kmeans_segmented(const float *pool, int C,
  *  proxy_sqnorm [n_seg, 2, kmax]   out
  */
 size_t aoc_build_proxies_workspace_bytes(int64_t rows_capacity, int n_seg, int kmax);
+/* Alignment ("Pointer alignment" above): class 16: pool, workspace; every other pointer class 4. */
 int aoc_build_proxies(const float *pool, int64_t pool_rows, int C, const int32_t *fg_rows,
                       const int32_t *seg_offsets, const int32_t *seg_k, const int32_t *labels,
                       const float *centroids, int n_seg, int kmax, int64_t rows_capacity,
@@ -200,6 +250,7 @@ int aoc_build_proxies(const float *pool, int64_t pool_rows, int C, const int32_t
  *               can land in its channel of the [O, 24, h, w] proto-mask buffer or in [1,h,w,O,F].
  *  transform    1 = apply the proto-mask transform, 0 = raw squared distance
  */
+/* Alignment ("Pointer alignment" above): class 16: proxies; every other pointer class 4. */
 int aoc_proxy_corr_min(const float *query, int64_t m, int C,
                        const float *proxies, const float *proxy_sqnorm, int n_proxy,
                        int n_set, const int32_t *set_begin_host, const int32_t *set_size_host,
@@ -210,6 +261,7 @@ int aoc_proxy_corr_min(const float *query, int64_t m, int C,
  * the distances are rounded to float16 where the reference's float16 tensors round them (sums accumulate in fp32, as torch does);
  * proxy_sqnorm is only consulted for its +inf "absent" marks.  Outputs are fp32 (the bias is added and the sigmoid taken in fp32, as the
  * reference's type promotion does). */
+/* Alignment ("Pointer alignment" above): class 16: proxies; every other pointer class 4. */
 int aoc_proxy_corr_min_f16(const float *query, int64_t m, int C,
                            const float *proxies, const float *proxy_sqnorm, int n_proxy,
                            int n_set, const int32_t *set_begin_host, const int32_t *set_size_host,
@@ -233,6 +285,7 @@ int aoc_proxy_corr_min_f16(const float *query, int64_t m, int C,
  *  workspace: aoc_proxy_corr_min_batched_workspace_bytes() bytes (the device-side take-over flag: the kernel stores the call's sequence
  *            number there when a precondition fails and the gated fp32 kernel runs iff it finds it).  Zero it once after allocation and
  *            use it from one stream at a time; the calls themselves never reset it. */
+/* Alignment ("Pointer alignment" above): class 16: query, proxies; every other pointer class 4. */
 typedef struct aoc_corr_frame {
     const float *query;         /* [m, C] */
     const float *proxies;       /* [n_proxy, C] */
@@ -242,6 +295,7 @@ typedef struct aoc_corr_frame {
 } aoc_corr_frame;
 enum aoc_corr_precision { AOC_CORR_SPLIT = 0, AOC_CORR_FP32 = 1 };
 size_t aoc_proxy_corr_min_batched_workspace_bytes(void);
+/* Alignment ("Pointer alignment" above): class 16: -; every other pointer class 4. */
 int aoc_proxy_corr_min_batched(const aoc_corr_frame *frames_host, int n_frames, int64_t m, int C, int n_proxy, int n_set,
                                const int32_t *set_begin_host, const int32_t *set_size_host,
                                const int64_t *set_out_offset_host, int transform, int precision,
@@ -253,6 +307,7 @@ int aoc_proxy_corr_min_batched(const aoc_corr_frame *frames_host, int n_frames, 
  * fp16-split arithmetic (C = 100) with the same device-side take-over by the exact-fp32 kernel (which reads `query`); results equal
  * aoc_proxy_corr_min_batched(precision = AOC_CORR_SPLIT) up to the summation order of |q|^2 (query_sqnorm is the sequential sum).
  * Same workspace as aoc_proxy_corr_min_batched. */
+/* Alignment ("Pointer alignment" above): class 16: query_rec, proxies; every other pointer class 4. */
 typedef struct aoc_corr_frame_rec {
     const float *query;         /* [m, C] fp32 rows (take-over only) */
     const void *query_rec;      /* aoc_split_rows_tiled(query) */
@@ -262,6 +317,7 @@ typedef struct aoc_corr_frame_rec {
     const float *set_bias;      /* [n_set] or NULL */
     float *out;
 } aoc_corr_frame_rec;
+/* Alignment ("Pointer alignment" above): class 16: -; every other pointer class 4. */
 int aoc_proxy_corr_min_records(const aoc_corr_frame_rec *frames_host, int n_frames, int64_t m, int C, int n_proxy, int n_set,
                                const int32_t *set_begin_host, const int32_t *set_size_host,
                                const int64_t *set_out_offset_host, int transform,
@@ -274,6 +330,7 @@ int aoc_proxy_corr_min_records(const aoc_corr_frame_rec *frames_host, int n_fram
  * cached, one per workspace -- does not match the call's set structure (a sequence writes them once).  tables_key = NULL: the plain call.
  * Results are identical to aoc_proxy_corr_min_records (every workgroup runs the same code on the same pass). */
 size_t aoc_proxy_corr_min_records_cached_workspace_bytes(void);
+/* Alignment ("Pointer alignment" above): class 16: workspace; every other pointer class 4. */
 int aoc_proxy_corr_min_records_cached(const aoc_corr_frame_rec *frames_host, int n_frames, int64_t m, int C, int n_proxy, int n_set,
                                       const int32_t *set_begin_host, const int32_t *set_size_host,
                                       const int64_t *set_out_offset_host, int transform,
@@ -289,6 +346,7 @@ int aoc_proxy_corr_min_records_cached(const aoc_corr_frame_rec *frames_host, int
  *  n_fg == 0 yields 1.0 everywhere when transform != 0 (AEM:796-797), +inf otherwise.
  */
 size_t aoc_dense_match_workspace_bytes(int64_t m, int64_t n_fg_capacity, int n_obj);
+/* Alignment ("Pointer alignment" above): class 16: pool; every other pointer class 4. */
 int aoc_dense_match_min(const float *query, int64_t m, int C,
                         const float *pool, const int32_t *fg_rows, const int32_t *n_fg,
                         int64_t n_fg_capacity, const uint32_t *wrong_bits,
@@ -299,6 +357,7 @@ int aoc_dense_match_min(const float *query, int64_t m, int C,
 /* use_float16=True (AEM:801-803 `.half()`; AEM:65-66 the wrong-label mask becomes float16 too): same arguments and workspace as
  * aoc_dense_match_min; operands, norms, dot products, distances, the 5e4 padding (49984 in float16) and its sum are rounded to float16
  * where the reference's float16 tensors round them (sums accumulate in fp32).  Outputs are fp32. */
+/* Alignment ("Pointer alignment" above): class 16: pool; every other pointer class 4. */
 int aoc_dense_match_min_f16(const float *query, int64_t m, int C,
                             const float *pool, const int32_t *fg_rows, const int32_t *n_fg,
                             int64_t n_fg_capacity, const uint32_t *wrong_bits,
@@ -318,6 +377,7 @@ int aoc_dense_match_min_f16(const float *query, int64_t m, int C,
  * when *n_fg == 0 -- T is exactly 1.0f there and the gradient zero.  out holds bit for bit the values of aoc_dense_match_min (the same
  * tile routine; an index rides beside each minimum).  1 .. AOC_MAX_OBJECTS objects, C as aoc_dense_match_min. */
 size_t aoc_dense_match_argmin_workspace_bytes(int64_t m, int64_t n_fg_capacity, int n_obj);
+/* Alignment ("Pointer alignment" above): class 16: pool; every other pointer class 4. */
 int aoc_dense_match_argmin(const float *query, int64_t m, int C,
                            const float *pool, const int32_t *fg_rows, const int32_t *n_fg,
                            int64_t n_fg_capacity, const uint32_t *wrong_bits,
@@ -335,6 +395,7 @@ int aoc_dense_match_argmin(const float *query, int64_t m, int C,
  * fixed order (ascending pixel, then object; long lists over a fixed tree of pair-id ranges), so the same buffers give the same bits.
  * C <= AOC_MAX_CHANNELS, n_obj <= AOC_MAX_OBJECTS. */
 size_t aoc_dense_match_grad_workspace_bytes(int64_t m, int64_t n, int C, int n_obj);
+/* Alignment ("Pointer alignment" above): class 16: -; every other pointer class 4. */
 int aoc_dense_match_grad(const float *grad_out, const float *T, const int32_t *arg, int64_t pixel_stride, int64_t obj_stride,
                          const float *query, int64_t m, int C, const float *pool, int64_t n, int n_obj,
                          float *grad_query, float *grad_pool, float *grad_bias,
@@ -347,6 +408,7 @@ int aoc_dense_match_grad(const float *grad_out, const float *T, const int32_t *a
  *   grad_bias [n_obj]       = sum_i g
  * Each output may be NULL.  Deterministic like aoc_dense_match_grad. */
 size_t aoc_proxy_match_grad_workspace_bytes(int64_t m, int C, int n_obj);
+/* Alignment ("Pointer alignment" above): class 16: -; every other pointer class 4. */
 int aoc_proxy_match_grad(const float *grad_out, const float *T, int64_t pixel_stride, int64_t obj_stride,
                          const float *query, int64_t m, int C, const float *proxies, int n_obj,
                          float *grad_query, float *grad_proxies, float *grad_bias,
@@ -387,12 +449,15 @@ int aoc_proxy_match_grad(const float *grad_out, const float *T, int64_t pixel_st
  *                              out / strides / transform as aoc_dense_match_min.  n_obj <= 16.
  */
 size_t aoc_split_record_bytes(int C);
+/* Alignment ("Pointer alignment" above): class 16: x, records; every other pointer class 4. */
 int aoc_split_rows(const float *x, int64_t n, int C, void *records, float *sqnorm,
                    int32_t *overflow_flag, aoc_stream_t stream);
 size_t aoc_split_rows_tiled_bytes(int64_t n, int C);
+/* Alignment ("Pointer alignment" above): class 16: x, records; every other pointer class 4. */
 int aoc_split_rows_tiled(const float *x, int64_t n, int C, void *records, float *sqnorm,
                          int32_t *overflow_flag, aoc_stream_t stream);
 size_t aoc_dense_match_split_workspace_bytes(int64_t m, int64_t n, int n_obj);
+/* Alignment ("Pointer alignment" above): class 16: query, query_rec, pool, pool_rec, workspace; every other pointer class 4. */
 int aoc_dense_match_min_split(const float *query, const void *query_rec, const float *query_sqnorm, int query_rec_tiled,
                               int64_t m, int C, const float *pool, const void *pool_rec,
                               const int32_t *overflow_flag, int64_t n,
@@ -418,6 +483,7 @@ int aoc_dense_match_min_split(const float *query, const void *query_rec, const f
  *  - an object with counts[o] = 0 has a bounds column that no kernel reads or writes: it keeps the zeros of the build;
  *  - m, n, n_obj and C are those of the build (they place the plan inside the workspace); a new pool state, of any size that fits,
  *    starts with reuse_plan = 0 in the same bytes. */
+/* Alignment ("Pointer alignment" above): class 16: query, query_rec, pool, pool_rec, workspace; every other pointer class 4. */
 int aoc_dense_match_min_split_cached(const float *query, const void *query_rec, const float *query_sqnorm, int query_rec_tiled,
                               int64_t m, int C, const float *pool, const void *pool_rec,
                               const int32_t *overflow_flag, int64_t n,
@@ -471,6 +537,7 @@ int aoc_dense_match_set_probe(void *start_event, void *stop_event);
  *  out           [n_obj, n_radii, H, W]; channel order [max, r_0, r_1, ...] (AEM:1034-1046);
  *                value = transform(min over the window of masked distances; 5e4 if none)
  */
+/* Alignment ("Pointer alignment" above): class 16: query, prev; every other pointer class 4. */
 int aoc_local_window_match(const float *query, const float *prev, const uint32_t *right_bits,
                            int H, int W, int C, const int32_t *radii_host, int n_radii,
                            const float *obj_bias, int n_obj, float *out, int transform,
@@ -481,6 +548,7 @@ int aoc_local_window_match(const float *query, const float *prev, const uint32_t
  *                nested windows are radii / rate rings (AEM:1039);
  *   float16      use_float16=True (AEM:1002-1005): operands, norms, dot products and distances are rounded to float16 exactly where the
  *                reference's float16 tensors round them (the sums accumulate in fp32 as torch does); outputs are fp32. */
+/* Alignment ("Pointer alignment" above): class 16: query, prev; every other pointer class 4. */
 int aoc_local_window_match_ex(const float *query, const float *prev, const uint32_t *right_bits,
                               int H, int W, int C, const int32_t *radii_host, int n_radii,
                               const float *obj_bias, int n_obj, float *out, int transform,
@@ -488,8 +556,10 @@ int aoc_local_window_match_ex(const float *query, const float *prev, const uint3
 
 /* Bilinear (align_corners=True) resize of a channel-last map [h,w,C] -> [H,W,C]  (AEM:938-941).  _ex with float16 != 0: the resize
  * of a float16 tensor (float16 samples, fp32 arithmetic, float16 result), as F.interpolate does in the use_float16 mode. */
+/* Alignment ("Pointer alignment" above): class 16: -; every other pointer class 4. */
 int aoc_resize_bilinear_hwc(const float *in, int h, int w, int C, float *out, int H, int W,
                             aoc_stream_t stream);
+/* Alignment ("Pointer alignment" above): class 16: -; every other pointer class 4. */
 int aoc_resize_bilinear_hwc_ex(const float *in, int h, int w, int C, float *out, int H, int W,
                                int float16, aoc_stream_t stream);
 /* Bilinear (align_corners=True) resize of planes [P,h,w]; plane p = (po, pi) = (p / inner_count,
@@ -504,8 +574,10 @@ int aoc_resize_bilinear_planes(const float *in, int P, int h, int w, float *out,
 /* Atrous sub-sampling of a channel-last map (AEM:533-579, the atrous_obj_pixel_num == 0 branch: pad to a multiple of the rate, view as
  * [h', rate, w', rate, X], keep [:, 0, :, 0]): out [h', w', X] = in[rate * y', rate * x', :] with h' = ceil(h / rate), w' = ceil(w / rate) -- the
  * padding is never selected.  For the embeddings AND the label maps of a pool frame (a device-side gather: no host-side pad / view arithmetic). */
+/* Alignment ("Pointer alignment" above): class 16: in, out; every other pointer class 4. */
 int aoc_atrous_subsample(const float *in, int h, int w, int X, int rate, float *out, aoc_stream_t stream);
 /* torch 'nearest' resize of per-pixel label bits [h,w] -> [H,W]  (AEM:1017-1018). */
+/* Alignment ("Pointer alignment" above): class 16: -; every other pointer class 4. */
 int aoc_resize_nearest_bits(const uint32_t *in, int h, int w, uint32_t *out, int H, int W,
                             aoc_stream_t stream);
 
@@ -520,6 +592,7 @@ int aoc_resize_nearest_bits(const uint32_t *in, int h, int w, uint32_t *out, int
  * cy * W + cx that holds the minimum of that channel's window; ties go to the lowest pixel index (row-major window order, the first
  * occurrence) in every nested window alike; -1 where the value is the padding (no right pixel in the window): out is then exactly 1.0f
  * with transform != 0 and the gradient is zero. */
+/* Alignment ("Pointer alignment" above): class 16: query, prev; every other pointer class 4. */
 int aoc_local_window_match_argmin(const float *query, const float *prev, const uint32_t *right_bits, int H, int W, int C,
                                   const int32_t *radii_host, int n_radii, const float *obj_bias, int n_obj,
                                   float *out, int32_t *arg, int transform, int atrous_rate, aoc_stream_t stream);
@@ -535,6 +608,7 @@ int aoc_local_window_match_argmin(const float *query, const float *prev, const u
  * order fixed by the source: the same buffers give the same bits.  C <= AOC_MAX_CHANNELS, n_radii <= 8, n_obj <= AOC_MAX_OBJECTS,
  * 0 <= window <= 31. */
 size_t aoc_local_match_grad_workspace_bytes(int H, int W, int C, int n_radii, int n_obj);
+/* Alignment ("Pointer alignment" above): class 16: -; every other pointer class 4. */
 int aoc_local_match_grad(const float *grad_out, const float *T, const int32_t *arg,
                          const float *query, const float *prev, int H, int W, int C, int n_radii, int n_obj, int window,
                          float *grad_query, float *grad_prev, float *grad_bias,
@@ -553,6 +627,7 @@ int aoc_local_match_grad(const float *grad_out, const float *T, const int32_t *a
  * 4 .. AOC_MAX_CHANNELS), set sizes 0 .. AOC_MAX_CLUSTERS (beyond: AOC_ERR_UNSUPPORTED), any number of sets (a frame has
  * 2 * levels * objects of them; 64 go into one launch).  No workspace.  proxy_sqnorm = NULL is the slow form: every lane sums |p|^2 over
  * all C again for every tile of 16 query pixels. */
+/* Alignment ("Pointer alignment" above): class 16: -; every other pointer class 4. */
 int aoc_proxy_set_match_argmin(const float *query, int64_t m, int C,
                                const float *proxies, const float *proxy_sqnorm, int n_proxy,
                                int n_set, const int32_t *set_begin_host, const int32_t *set_size_host,
@@ -575,6 +650,7 @@ int aoc_proxy_set_match_argmin(const float *query, int64_t m, int C,
  * in m (at most 128 chunks), it never holds a [m, n_proxy, C] term.  Only needed when grad_proxies or grad_bias is wanted.
  * C and set sizes as the forward; set_bias_index may be NULL when grad_bias is. */
 size_t aoc_proxy_set_match_grad_workspace_bytes(int64_t m, int C, int64_t n_slot);
+/* Alignment ("Pointer alignment" above): class 16: -; every other pointer class 4. */
 int aoc_proxy_set_match_grad(const float *grad_out, const float *T, const int32_t *arg, int64_t pixel_stride,
                              const float *query, int64_t m, int C, const float *proxies, int n_proxy,
                              int n_set, const int32_t *set_begin_host, const int32_t *set_size_host,
@@ -591,6 +667,7 @@ int aoc_proxy_set_match_grad(const float *grad_out, const float *T, const int32_
  * kept position: a row shared by several segments needs neither atomics nor ordering.  Multi-level segment lists
  * (n_seg = levels * objects, aoc_kmeans_replicate_levels) are segments like any other.  workspace: the counts, [n_seg, kmax] int32. */
 size_t aoc_centroid_avg_grad_workspace_bytes(int n_seg, int kmax);
+/* Alignment ("Pointer alignment" above): class 16: -; every other pointer class 4. */
 int aoc_centroid_avg_grad(const float *grad_proxies, int C, const int32_t *fg_rows, const int32_t *n_fg,
                           const int32_t *seg_offsets, const int32_t *seg_k, const int32_t *labels,
                           int n_seg, int kmax, int64_t rows_capacity, float *grad_pool, int64_t pool_rows,
@@ -879,6 +956,7 @@ int aoc_resize_bilinear_planes_grouped(const float *in, int P, int h, int w, flo
 
 /* local_matching AND local_matching_proxy (AEM:968-1156 as aocnet.py:255,328 calls them: same query, same label bits, fp32, atrous rate 1)
  * in one launch: out_a from prev_a (the previous frame's embedding), out_b from prev_b (its per-pixel proxy map). */
+/* Alignment ("Pointer alignment" above): class 16: query, prev_a, prev_b; every other pointer class 4. */
 int aoc_local_window_match_pair(const float *query, const float *prev_a, const float *prev_b, const uint32_t *right_bits, int H, int W, int C,
                                 const int32_t *radii_host, int n_radii, const float *obj_bias, int n_obj, float *out_a, float *out_b,
                                 int transform, aoc_stream_t stream);
@@ -890,6 +968,7 @@ int aoc_local_window_match_pair(const float *query, const float *prev_a, const f
  * Optional small tables filled by the same launch (NULL / 0 = off): set_bias_out [n_pair_sets + n_obj] = the per-set bias table of the
  * correlation launch (set s < n_pair_sets belongs to object (s / 2) % n_obj, set n_pair_sets + o to object o); two float copies
  * copy_dst_x[0 .. n_copy_x) = copy_src_x[..] (the pooled reference heads into the k = 1 rows of the proxy table). */
+/* Alignment ("Pointer alignment" above): class 16: -; every other pointer class 4. */
 int aoc_local_prep(const float *cur_emb, const float *prev_emb, const float *prev_labels, const float *prev_pos, int h, int w, int C, int n_obj,
                    float *q2, float *p2, float *pm2, uint32_t *bits2, int H2, int W2,
                    const float *obj_bias, int n_pair_sets, float *set_bias_out,
@@ -900,6 +979,7 @@ int aoc_local_prep(const float *cur_emb, const float *prev_emb, const float *pre
  * channels [ch_local_bg, +n_local) = foreground2background of [ch_local, +n_local), channel ch_global_bg = foreground2background of
  * ch_global, channel ch_prev_mask = prev_labels [hw, n_obj] transposed; head [n_obj, 4 C] = (ref_pos | ref_neg | prev_pos | prev_neg),
  * ATT:188.  A channel index < 0 / head == NULL switches that part off. */
+/* Alignment ("Pointer alignment" above): class 16: -; every other pointer class 4. */
 int aoc_proto_finish(float *feat, int n_obj, int64_t hw, int64_t obj_stride, int ch_local, int n_local, int ch_local_bg, int ch_global, int ch_global_bg,
                      int ch_prev_mask, const float *prev_labels, const float *ref_pos, const float *ref_neg, const float *prev_pos, const float *prev_neg,
                      int C, float *head, aoc_stream_t stream);
@@ -909,6 +989,7 @@ int aoc_proto_finish(float *feat, int n_obj, int64_t hw, int64_t obj_stride, int
  * and reduces that dim, so  out[o, 0, x] = min over o' != o and over channels c of dis[o', c, x].
  *  dis: object o at dis + o*dis_obj_stride holds [n_ch, inner]; out: object o at out + o*out_obj_stride
  *  holds [inner]; n_obj >= 2 (n_obj == 1 returns the input, AEM:10-11). */
+/* Alignment ("Pointer alignment" above): class 16: -; every other pointer class 4. */
 int aoc_fg2bg_min(const float *dis, int n_obj, int n_ch, int64_t inner, int64_t dis_obj_stride,
                   float *out, int64_t out_obj_stride, aoc_stream_t stream);
 
@@ -1190,6 +1271,7 @@ int aoc_mask_jf_accumulate(const int32_t *pred, const int32_t *gt, int H, int W,
  *
  * Output channels of feat [n_obj, n_ch, h, w], n_ch = aoc_frame_channels(): global(1) | cluster (centroid, centroid_avg) per level |
  * proxy(1) | local(n_radii) | local_proxy(n_radii) | prev_mask(1) [| local_bg(n_radii) | global_bg(1)]. */
+/* Alignment ("Pointer alignment" above): class 16: ref_emb, match_emb, prev_emb, cur_emb, proxy_table; every other pointer class 4. */
 typedef struct aoc_frame_desc {
     int32_t h, w, C, n_obj;          /* map size, embedding width, objects incl. background */
     int32_t R, R_capacity;           /* pool frames this frame sees / the workspace was sized for */
@@ -1237,6 +1319,7 @@ typedef struct aoc_seq_state {
 } aoc_seq_state;
 int aoc_frame_channels(int n_radii, int n_levels, int matching_background);
 size_t aoc_frame_workspace_bytes(int h, int w, int C, int n_obj, int R_capacity, int n_radii, int n_levels);
+/* Alignment ("Pointer alignment" above): class 16: workspace; every other pointer class 4. */
 int aoc_frame_enqueue(const aoc_frame_desc *desc, aoc_seq_state *state, void *workspace, size_t workspace_bytes, aoc_stream_t stream);
 
 /* The adaptive proxies of the frames that see ONE pool state as ONE call (round 5): what hotpath.launch_cluster_proxies_batch issued as
@@ -1244,6 +1327,7 @@ int aoc_frame_enqueue(const aoc_frame_desc *desc, aoc_seq_state *state, void *wo
  * iterations, AEM:252-279), aoc_build_proxies (AEM:280-282) and the scatter of every frame's proxies into ITS proxy table -- out of one
  * caller-owned workspace, enqueued on `stream` (the caller's side stream) without host synchronisation.  Bit-identical to the three calls.
  * With aoc_frame_enqueue and aoc_gates_enqueue a frame of the orchestrated path is three C calls (one per stream it touches). */
+/* Alignment ("Pointer alignment" above): class 16: pool, tables; every other pointer class 4. */
 typedef struct aoc_chain_desc {
     int32_t C, n_obj, n_frames;      /* embedding width, objects incl. background, frames F that see this pool state (<= 8) */
     int32_t n_levels, levels[8];     /* cluster_num per level (AEM:232) */
@@ -1262,6 +1346,7 @@ size_t aoc_cluster_chain_workspace_bytes(const aoc_chain_desc *desc);
  * [1] labels [n_frames * n_levels * rows_capacity] int32, [2] cluster counts [S, kmax] int32, [3] proxies [S, 2, kmax, C] float,
  * [4] proxy squared norms [S, 2, kmax] float, [5] seg_k [S] int32, [6] seg_offsets [S + 1] int32;  S = n_frames * n_levels * n_obj */
 int aoc_cluster_chain_layout(const aoc_chain_desc *desc, int64_t *offsets7);
+/* Alignment ("Pointer alignment" above): class 16: workspace; every other pointer class 4. */
 int aoc_cluster_chain_enqueue(const aoc_chain_desc *desc, void *workspace, size_t workspace_bytes, aoc_stream_t stream);
 
 /* The modulation gates of CalibrationDecoding.forward (decoding_module.py:96-149, 162-210) as ONE call: a list of gate descriptors, every

@@ -16,6 +16,11 @@
 static inline hipStream_t aoc_hip_stream(aoc_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 static inline size_t aoc_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// The alignment contract of include/aoc_hip.h, host side: true when one of the pointers is off the 16-byte grid (NULL is on it).  Every entry
+// asks this of its class-16 pointers -- the ones a kernel reaches through float4 / uint4 or an LDS-direct load -- before it enqueues anything.
+template <typename... P>
+static inline bool aoc_off16(P... p) { return ((reinterpret_cast<uintptr_t>(static_cast<const void *>(p)) | ...) & 15) != 0; }
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // Proto-mask transform of AEM:393/602/808/1049: (sigmoid(d + bias) - 0.5) * 2.

@@ -601,6 +601,7 @@ int aoc_proxy_corr_min(const float *query, int64_t m, int C, const float *proxie
                        int n_set, const int32_t *set_begin_host, const int32_t *set_size_host, const int64_t *set_out_offset_host,
                        const float *set_bias, float *out, int64_t out_pixel_stride, int transform, aoc_stream_t stream) {
     if (!query || !proxies || !out) return AOC_ERR_INVALID_ARG;
+    if (aoc_off16(proxies)) return AOC_ERR_INVALID_ARG;                    // stage_tile_rows reads the proxy rows as float4
     const aoc_corr_frame fr = {query, proxies, proxy_sqnorm, set_bias, out};
     return aoc_corr_fp32_batched(&fr, 1, m, C, n_proxy, n_set, set_begin_host, set_size_host, set_out_offset_host, out_pixel_stride, transform,
                                  nullptr, stream, 0);
@@ -610,6 +611,7 @@ int aoc_proxy_corr_min_f16(const float *query, int64_t m, int C, const float *pr
                            int n_set, const int32_t *set_begin_host, const int32_t *set_size_host, const int64_t *set_out_offset_host,
                            const float *set_bias, float *out, int64_t out_pixel_stride, int transform, aoc_stream_t stream) {
     if (!query || !proxies || !out) return AOC_ERR_INVALID_ARG;
+    if (aoc_off16(proxies)) return AOC_ERR_INVALID_ARG;                    // stage_tile_rows reads the proxy rows as float4
     const aoc_corr_frame fr = {query, proxies, proxy_sqnorm, set_bias, out};
     return aoc_corr_fp32_batched(&fr, 1, m, C, n_proxy, n_set, set_begin_host, set_size_host, set_out_offset_host, out_pixel_stride, transform,
                                  nullptr, stream, 1);
@@ -739,6 +741,7 @@ int aoc_dense_match_min_gated(const float *query, int64_t m, int C, const float 
                               float *out, int64_t out_pixel_stride, int64_t out_obj_stride, int transform,
                               void *workspace, size_t workspace_bytes, const int32_t *gate, aoc_stream_t stream, int float16) {
     if (!query || !pool || !fg_rows || !n_fg || !wrong_bits || !out || !workspace) return AOC_ERR_INVALID_ARG;
+    if (aoc_off16(pool)) return AOC_ERR_INVALID_ARG;                       // issue_rows reads the pool rows as float4
     if (m < 1 || C < 4 || n_obj < 1 || n_fg_capacity < 1 || n_fg_capacity >= (1ll << 31)) return AOC_ERR_INVALID_ARG;
     if ((C & 3) || C > 128 || n_obj > AOC_MAX_OBJECTS) return AOC_ERR_UNSUPPORTED;
     if (workspace_bytes < aoc_dense_match_workspace_bytes(m, n_fg_capacity, n_obj)) return AOC_ERR_WORKSPACE;

@@ -751,9 +751,12 @@ int cb_run(const aoc_corr_frame *frames_host, const AocCorrRecFrame *rec_host, i
         if (!frames_host[f].query || !frames_host[f].proxies || !frames_host[f].out) return AOC_ERR_INVALID_ARG;
     hipStream_t st = aoc_hip_stream(stream);
 
-    bool split_ok = precision == AOC_CORR_SPLIT && C == 100 && workspace && workspace_bytes >= CB_WS_BYTES;
-    for (int f = 0; f < n_frames && split_ok; ++f)
-        if ((reinterpret_cast<uintptr_t>(frames_host[f].query) | reinterpret_cast<uintptr_t>(frames_host[f].proxies)) & 15) split_ok = false;
+    // class-16 pointers (include/aoc_hip.h): every kernel of this file and the exact-fp32 kernel stage the proxy rows as float4; the batched
+    // kernel streams the fp32 query through 16-byte LDS-direct loads (the records form reads `query` with 4-byte loads, in the take-over only).
+    // A misaligned table used to switch the split path off here and went on to the fp32 kernel, whose staging needs the same 16 bytes.
+    for (int f = 0; f < n_frames; ++f)
+        if (aoc_off16(frames_host[f].proxies) || (!rec_host && aoc_off16(frames_host[f].query))) return AOC_ERR_INVALID_ARG;
+    const bool split_ok = precision == AOC_CORR_SPLIT && C == 100 && workspace && workspace_bytes >= CB_WS_BYTES;
     if (!split_ok) {
         if (precision == AOC_CORR_SPLIT && (!workspace || workspace_bytes < CB_WS_BYTES)) return AOC_ERR_WORKSPACE;
         return aoc_corr_fp32_batched(frames_host, n_frames, m, C, n_proxy, n_set, set_begin_host, set_size_host, set_out_offset_host, 1, transform,
@@ -1022,12 +1025,13 @@ int aoc_proxy_corr_min_records_cached(const aoc_corr_frame_rec *frames_host, int
     if (!frames_host || n_frames < 1 || n_frames > 4096) return AOC_ERR_INVALID_ARG;
     if (C != 100) return AOC_ERR_UNSUPPORTED;                                 // the records of dense_split.hip at the kernel's channel count
     if (!workspace || workspace_bytes < (tables_key ? CB_WS_CACHED_BYTES : CB_WS_BYTES)) return AOC_ERR_WORKSPACE;
+    if (tables_key && aoc_off16(workspace)) return AOC_ERR_INVALID_ARG;       // the cached tile tables have 8-byte members
     aoc_corr_frame *plain = static_cast<aoc_corr_frame *>(malloc(sizeof(aoc_corr_frame) * (size_t)n_frames));
     AocCorrRecFrame *rec = static_cast<AocCorrRecFrame *>(malloc(sizeof(AocCorrRecFrame) * (size_t)n_frames));
     int rc = (plain && rec) ? AOC_OK : AOC_ERR_LAUNCH;
     for (int f = 0; f < n_frames && rc == AOC_OK; ++f) {
         const aoc_corr_frame_rec &s = frames_host[f];
-        if (!s.query || !s.query_rec || !s.query_sqnorm || (reinterpret_cast<uintptr_t>(s.query_rec) & 15)) { rc = AOC_ERR_INVALID_ARG; break; }
+        if (!s.query || !s.query_rec || !s.query_sqnorm || aoc_off16(s.query_rec, s.proxies)) { rc = AOC_ERR_INVALID_ARG; break; }
         plain[f].query = s.query; plain[f].proxies = s.proxies; plain[f].proxy_sqnorm = s.proxy_sqnorm; plain[f].set_bias = s.set_bias; plain[f].out = s.out;
         rec[f].qrec = static_cast<const uint4 *>(s.query_rec); rec[f].q2 = s.query_sqnorm;
         rec[f].proxies = s.proxies; rec[f].sqnorm = s.proxy_sqnorm; rec[f].bias = s.set_bias; rec[f].out = s.out;

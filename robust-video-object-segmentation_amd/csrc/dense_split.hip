@@ -779,6 +779,7 @@ size_t aoc_split_record_bytes(int C) { return (C >= 4 && (C & 3) == 0 && C <= SP
 
 int aoc_split_rows(const float *x, int64_t n, int C, void *records, float *sqnorm, int32_t *overflow_flag, aoc_stream_t stream) {
     if (!x || !records || !overflow_flag || n < 0) return AOC_ERR_INVALID_ARG;
+    if (aoc_off16(x, records)) return AOC_ERR_INVALID_ARG;                 // float4 loads of the rows, uint4 stores of the records
     if (aoc_split_record_bytes(C) == 0) return AOC_ERR_UNSUPPORTED;
     if (n == 0) return AOC_OK;
     const int64_t total = n * SP_KS;
@@ -795,6 +796,7 @@ size_t aoc_split_rows_tiled_bytes(int64_t n, int C) {
 
 int aoc_split_rows_tiled(const float *x, int64_t n, int C, void *records, float *sqnorm, int32_t *overflow_flag, aoc_stream_t stream) {
     if (!x || !records || !overflow_flag || n < 0) return AOC_ERR_INVALID_ARG;
+    if (aoc_off16(x, records)) return AOC_ERR_INVALID_ARG;                 // float4 loads of the rows, uint4 stores of the records
     if (aoc_split_record_bytes(C) == 0) return AOC_ERR_UNSUPPORTED;
     if (n == 0) return AOC_OK;
     const int64_t total = (n + 31) / 32 * 32 * SP_KS;
@@ -827,6 +829,8 @@ int aoc_dense_match_min_split_cached(const float *query, const void *query_rec, 
     if (!query || !query_rec || !query_sqnorm || !pool || !pool_rec || !overflow_flag || !right_bits || !wrong_bits || !fg_rows ||
         !obj_rows || !counts || !obj_offsets || !out || !workspace)
         return AOC_ERR_INVALID_ARG;
+    // float4 rows in the seed and the exact-fp32 kernels, uint4 / LDS-direct records, LDS-direct tile lists out of the workspace
+    if (aoc_off16(query, query_rec, pool, pool_rec, workspace)) return AOC_ERR_INVALID_ARG;
     if (m < 1 || n < 1 || n >= (1ll << 31) - 4096 || n_obj < 1) return AOC_ERR_INVALID_ARG;
     if (aoc_split_record_bytes(C) == 0 || n_obj > 16) return AOC_ERR_UNSUPPORTED;
     if (workspace_bytes < aoc_dense_match_split_workspace_bytes(m, n, n_obj)) return AOC_ERR_WORKSPACE;

@@ -102,6 +102,8 @@ int aoc_frame_enqueue(const aoc_frame_desc *d, aoc_seq_state *state, void *works
     if (!d->ref_emb || !d->ref_labels || !d->prev_emb || !d->prev_labels || !d->cur_emb || !d->dis_bias || !d->right_bits || !d->wrong_bits ||
         !d->fg_rows || !d->obj_rows || !d->counts || !d->obj_offsets || !d->proxy_table || !d->proxy_sqnorm || !d->feat || !d->head)
         return AOC_ERR_INVALID_ARG;
+    // the class-16 pointers of the entries this call passes them to (split rows, dense pool, local previous map, proxy table, workspaces)
+    if (aoc_off16(d->ref_emb, d->match_emb, d->prev_emb, d->cur_emb, d->proxy_table, workspace)) return AOC_ERR_INVALID_ARG;
     if (d->h < 1 || d->w < 1 || d->n_obj < 1 || d->R < 1 || d->R > d->R_capacity || d->n_radii < 1 || d->n_radii > 8 || d->n_levels < 1 ||
         d->n_levels > 8 || d->kmax < 1 || d->pool_key == 0)
         return AOC_ERR_INVALID_ARG;
@@ -369,9 +371,10 @@ int aoc_cluster_chain_layout(const aoc_chain_desc *d, int64_t *offsets7) {
 int aoc_cluster_chain_enqueue(const aoc_chain_desc *d, void *workspace, size_t workspace_bytes, aoc_stream_t stream) {
     if (!chain_desc_ok(d) || !workspace) return AOC_ERR_INVALID_ARG;
     if (!d->pool || !d->fg_rows || !d->obj_rows || !d->obj_offsets || !d->init_rows) return AOC_ERR_INVALID_ARG;
+    if (aoc_off16(d->pool, workspace)) return AOC_ERR_INVALID_ARG;         // aoc_kmeans_segmented_rep / aoc_build_proxies: pool rows, workspaces
     if (d->C > AOC_MAX_CHANNELS || d->kmax > AOC_MAX_CLUSTERS || d->n_obj > AOC_MAX_OBJECTS || (d->C & 3)) return AOC_ERR_UNSUPPORTED;
     for (int f = 0; f < d->n_frames; ++f)
-        if (!d->tables[f] || !d->sqnorms[f] || (reinterpret_cast<uintptr_t>(d->tables[f]) & 15)) return AOC_ERR_INVALID_ARG;
+        if (!d->tables[f] || !d->sqnorms[f] || aoc_off16(d->tables[f])) return AOC_ERR_INVALID_ARG;      // chain_scatter_kernel's float4 stores
     if (workspace_bytes < aoc_cluster_chain_workspace_bytes(d)) return AOC_ERR_WORKSPACE;
     const ChainWs w = chain_carve(workspace, d);
     const int FL = d->n_frames * d->n_levels, S = FL * d->n_obj;

@@ -2580,6 +2580,9 @@ int aoc_kmeans_segmented_rep(const float *pool, int64_t pool_rows, int C, const 
     if (n_rep < 1 || (n_seg > 0 && n_seg % n_rep != 0)) return AOC_ERR_INVALID_ARG;
     if (!pool || !rows || !seg_offsets || !seg_k || !init_rows || !centroids || !labels || !cluster_counts || !workspace)
         return AOC_ERR_INVALID_ARG;
+    // float4 / 16-byte buffer and LDS-direct loads of the pool rows, float4 reads of the code book, float4 chunk sums and LDS-direct member
+    // lists in the workspace
+    if (aoc_off16(pool, centroids, workspace)) return AOC_ERR_INVALID_ARG;
     if (C < 1 || n_seg < 1 || kmax < 1 || iters < 1 || rows_capacity < 1 || rows_capacity >= (1ll << 31)) return AOC_ERR_INVALID_ARG;
     if (C > AOC_MAX_CHANNELS || kmax > AOC_MAX_CLUSTERS || n_seg > 65535) return AOC_ERR_UNSUPPORTED;
     if (workspace_bytes < aoc_kmeans_workspace_bytes(rows_capacity, n_seg, kmax, C)) return AOC_ERR_WORKSPACE;
@@ -2722,6 +2725,7 @@ int aoc_build_proxies(const float *pool, int64_t pool_rows, int C, const int32_t
                       const int32_t *labels, const float *centroids, int n_seg, int kmax, int64_t rows_capacity,
                       float *proxies, float *proxy_sqnorm, void *workspace, size_t workspace_bytes, aoc_stream_t stream) {
     if (!pool || !fg_rows || !seg_offsets || !seg_k || !labels || !centroids || !proxies || !proxy_sqnorm) return AOC_ERR_INVALID_ARG;
+    if (aoc_off16(pool, workspace)) return AOC_ERR_INVALID_ARG;            // the ordered mean's LDS-direct loads of the pool rows and member lists
     if (C < 1 || n_seg < 1 || kmax < 1) return AOC_ERR_INVALID_ARG;
     if (C > AOC_MAX_CHANNELS || kmax > AOC_MAX_CLUSTERS || n_seg > 65535) return AOC_ERR_UNSUPPORTED;
     hipStream_t st = aoc_hip_stream(stream);

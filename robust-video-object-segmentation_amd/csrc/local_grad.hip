@@ -407,6 +407,7 @@ int aoc_local_window_match_argmin(const float *query, const float *prev, const u
                                   const int32_t *radii_host, int n_radii, const float *obj_bias, int n_obj,
                                   float *out, int32_t *arg, int transform, int atrous_rate, aoc_stream_t stream) {
     if (!query || !prev || !right_bits || !radii_host || !out || !arg) return AOC_ERR_INVALID_ARG;
+    if (aoc_off16(query, prev)) return AOC_ERR_INVALID_ARG;                // float4 pixel rows in both kernels
     if (H < 1 || W < 1 || C < 4 || n_radii < 1 || n_obj < 1 || atrous_rate < 1) return AOC_ERR_INVALID_ARG;
     if ((C & 3) || C > 128 || n_radii > LG_MAX_RADII || n_obj > AOC_MAX_OBJECTS) return AOC_ERR_UNSUPPORTED;
     if ((int64_t)H * W >= (1ll << 31) - 1) return AOC_ERR_UNSUPPORTED;                 // the pixel index is a key's low word, -1 is "none"

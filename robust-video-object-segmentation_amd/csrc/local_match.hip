@@ -549,6 +549,7 @@ int aoc_local_window_match_pair(const float *query, const float *prev_a, const f
                                 const int32_t *radii_host, int n_radii, const float *obj_bias, int n_obj, float *out_a, float *out_b,
                                 int transform, aoc_stream_t stream) {
     if (!prev_b || !out_b) return AOC_ERR_INVALID_ARG;
+    if (aoc_off16(query, prev_a, prev_b)) return AOC_ERR_INVALID_ARG;      // before the first of the two launches of the other widths
     if (C == 100 || C == 128)      // the register-operand kernel takes both maps as one launch (grid z)
         return local_window_match_impl(query, prev_a, right_bits, H, W, C, radii_host, n_radii, obj_bias, n_obj, out_a, transform, 1, 0, stream, prev_b, out_b);
     const int rc = local_window_match_impl(query, prev_a, right_bits, H, W, C, radii_host, n_radii, obj_bias, n_obj, out_a, transform, 1, 0, stream, nullptr, nullptr);
@@ -560,6 +561,7 @@ static int local_window_match_impl(const float *query, const float *prev, const 
                                    const int32_t *radii_host, int n_radii, const float *obj_bias, int n_obj,
                                    float *out, int transform, int atrous_rate, int float16, aoc_stream_t stream, const float *prev2, float *out2) {
     if (!query || !prev || !right_bits || !radii_host || !out) return AOC_ERR_INVALID_ARG;
+    if (aoc_off16(query, prev, prev2)) return AOC_ERR_INVALID_ARG;         // float4 pixel rows (both kernels read prev so, the register kernel query too)
     if (H < 1 || W < 1 || C < 4 || n_radii < 1 || n_obj < 1 || atrous_rate < 1) return AOC_ERR_INVALID_ARG;
     if ((C & 3) || C > 128 || n_radii > LM_MAX_RADII || n_obj > AOC_MAX_OBJECTS) return AOC_ERR_UNSUPPORTED;
     LocalRadii radii;
@@ -661,7 +663,7 @@ int aoc_local_prep(const float *cur_emb, const float *prev_emb, const float *pre
 
 int aoc_atrous_subsample(const float *in, int h, int w, int X, int rate, float *out, aoc_stream_t stream) {
     if (!in || !out || h < 1 || w < 1 || X < 1 || rate < 1) return AOC_ERR_INVALID_ARG;
-    if (((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) && (X & 3) == 0) return AOC_ERR_INVALID_ARG;
+    if (aoc_off16(in, out) && (X & 3) == 0) return AOC_ERR_INVALID_ARG;    // the 16-byte moves of X % 4 == 0; other X move 4 bytes at a time
     const int H = (h + rate - 1) / rate, W = (w + rate - 1) / rate;
     const int64_t total = (int64_t)H * W * ((X & 3) == 0 ? X >> 2 : X);
     hipLaunchKernelGGL(atrous_subsample_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, aoc_hip_stream(stream), in, w, X, rate, out, H, W);

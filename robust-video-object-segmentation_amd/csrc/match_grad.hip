@@ -284,6 +284,7 @@ int aoc_dense_match_argmin(const float *query, int64_t m, int C, const float *po
                            float *out, int32_t *arg, int64_t out_pixel_stride, int64_t out_obj_stride, int transform,
                            void *workspace, size_t workspace_bytes, aoc_stream_t stream) {
     if (!query || !pool || !fg_rows || !n_fg || !wrong_bits || !out || !arg || !workspace) return AOC_ERR_INVALID_ARG;
+    if (aoc_off16(pool)) return AOC_ERR_INVALID_ARG;                       // dense_match_partial_kernel reads the pool rows as float4
     if (m < 1 || C < 4 || n_obj < 1 || n_fg_capacity < 1 || n_fg_capacity >= (1ll << 31)) return AOC_ERR_INVALID_ARG;
     if ((C & 3) || C > 128 || n_obj > AOC_MAX_OBJECTS) return AOC_ERR_UNSUPPORTED;      // the widths of aoc_dense_match_min
     if (workspace_bytes < aoc_dense_match_argmin_workspace_bytes(m, n_fg_capacity, n_obj)) return AOC_ERR_WORKSPACE;

@@ -15,6 +15,11 @@ The tensor contract (the library reads bare pointers; tests/ops_contract_cases.p
     raises ValueError (AssertionError in the per-frame calls FrameCall / GateBatch, which assert instead of converting) BEFORE anything is
     enqueued, so the buffer is untouched.
   * Every address leaves through _p (ctypes arguments) or _addr (structure fields, pointer arrays), given a NAME, never a call expression.
+  * ALIGNMENT (include/aoc_hip.h, "Pointer alignment"; tests/alignment_cases.py has the class of every pointer): a pointer the kernels reach
+    through 16-byte accesses (class 16: embedding rows, proxy tables, split records) must sit on the 16-byte grid; the library refuses it
+    otherwise.  A slice such as buf.view(-1)[1:1 + n * C].view(n, C) is contiguous float32 and still off that grid.  _a16 copies such an
+    INPUT into a fresh tensor (bound to a name like every converted copy) and raises ValueError for such a caller-provided OUTPUT; every
+    other pointer (class 4: labels, bit masks, row lists, norms, biases, the strided destinations) may sit at any float boundary.
 """
 import ctypes
 import os
@@ -115,6 +120,18 @@ def _out(what, t, shape, dtype=torch.float32):
     return t
 
 
+def _a16(what, t, output=False):
+    """A class-16 pointer of the alignment contract (include/aoc_hip.h; a kernel reaches it through float4 / uint4 or an LDS-direct load): an
+    INPUT whose address is off the 16-byte grid becomes a fresh copy (the allocator's grid), a caller-provided OUTPUT raises ValueError --
+    outputs are never converted.  On the grid: one integer test, the tensor itself."""
+    if t is not None and (t.data_ptr() & 15) != 0:
+        if output:
+            raise ValueError(f"{what} does not start on the 16-byte grid: the kernels write it with 16-byte accesses "
+                             "(a caller-provided output is never copied behind the caller's back)")
+        t = t.clone()
+    return t
+
+
 def _span(what, t, need, dtype=torch.float32):
     """A buffer the library addresses with explicit strides from its data pointer (a channel slice of a larger tensor, the tail of a table):
     ValueError unless it is contiguous, has this dtype and holds at least `need` elements counted from its first."""
@@ -208,7 +225,7 @@ def kmeans_segmented(pool, rows, seg_offsets, seg_k, init_rows, kmax, iters=20, 
     """Segmented k-means, bit-identical to scipy kmeans2 (see include/aoc_hip.h).
     n_rep > 1: the segment lists are n_rep replicas of n_seg / n_rep base segments (kmeans_replicate[_levels]).
     Returns (centroids [S,kmax,C], labels [rows_capacity], cluster_counts [S,kmax])."""
-    pool = _f32c(pool)
+    pool = _a16("kmeans_segmented: pool", _f32c(pool))
     _need_gpu(pool, rows, seg_offsets, seg_k, init_rows)
     n_seg = seg_k.numel()
     C = pool.shape[1]
@@ -259,7 +276,7 @@ def kmeans_replicate_levels(rows, seg_offsets, n_seg, n_rep, levels, rows_capaci
 
 def build_proxies(pool, fg_rows, seg_offsets, seg_k, labels, centroids):
     """AEM:280-282 -> (proxies [S,2,kmax,C], proxy_sqnorm [S,2,kmax]); +inf norm = absent proxy."""
-    pool = _f32c(pool)
+    pool = _a16("build_proxies: pool", _f32c(pool))
     _need_gpu(pool, fg_rows, seg_offsets, seg_k, labels, centroids)
     fg_rows, seg_offsets, seg_k, labels, centroids = _i32c(fg_rows), _i32c(seg_offsets), _i32c(seg_k), _i32c(labels), _f32c(centroids)
     n_seg, kmax, C = centroids.shape
@@ -280,7 +297,7 @@ def proxy_corr_min(query_flat, proxies, proxy_sqnorm, set_begin, set_size, set_o
     out.data_ptr()[i*out_pixel_stride + set_out_offset[s]]  (see include/aoc_hip.h).  float16: the reference's `.half()` mode
     (aoc_proxy_corr_min_f16)."""
     query_flat = _f32c(query_flat)
-    proxies = _f32c(proxies)
+    proxies = _a16("proxy_corr_min: proxies", _f32c(proxies))
     proxy_sqnorm = _f32c(proxy_sqnorm) if proxy_sqnorm is not None else None
     _need_gpu(query_flat, proxies, proxy_sqnorm, out, set_bias)
     m, C = query_flat.shape
@@ -341,7 +358,7 @@ def proxy_corr_min_batched(frames, set_begin, set_size, set_out_offset, transfor
     arr = (_CorrFrame * len(frames))()
     keep = []
     for i, (q, p, sq, b, out) in enumerate(frames):
-        q, p = _f32c(q), _f32c(p)
+        q, p = _a16("proxy_corr_min_batched: query", _f32c(q)), _a16("proxy_corr_min_batched: proxies", _f32c(p))
         sq = _f32c(sq) if sq is not None else None
         b = _f32c(b) if b is not None else None
         _need_gpu(q, p, sq, b, out)
@@ -382,14 +399,14 @@ def proxy_corr_min_records(frames, set_begin, set_size, set_out_offset, transfor
     arr = (_CorrFrameRec * len(frames))()
     keep = []
     for i, (q, qs, p, sq, b, out) in enumerate(frames):
-        q, p = _f32c(q), _f32c(p)
+        q, p = _f32c(q), _a16("proxy_corr_min_records: proxies", _f32c(p))
         sq = _f32c(sq) if sq is not None else None
         b = _f32c(b) if b is not None else None
         _need_gpu(q, p, sq, b, out, qs.records, qs.sqnorm)
         assert qs.tiled and qs.n == m, "the records kernel reads aoc_split_rows_tiled records of the whole query"
         assert q.shape == (m, C) and p.shape == (n_proxy, C) and (b is None or b.numel() == n_set)
         _span("proxy_corr_min_records: out", out, int(so.max()) + m if n_set else 0)
-        rec, rsq = qs.records, qs.sqnorm
+        rec, rsq = _a16("proxy_corr_min_records: query records", qs.records), qs.sqnorm
         keep.append((q, p, sq, b, out, rec, rsq))
         arr[i] = _CorrFrameRec(_addr(q), _addr(rec), _addr(rsq), _addr(p), _addr(sq), _addr(b), _addr(out))
     vp = ctypes.c_void_p
@@ -422,7 +439,7 @@ def _dense_span(m, n_obj, pixel_stride, obj_stride):
 
 def dense_match_min(query_flat, pool, prep, obj_bias, out, out_pixel_stride, out_obj_stride, transform=True, float16=False):
     query_flat = _f32c(query_flat)
-    pool = _f32c(pool)
+    pool = _a16("dense_match_min: pool", _f32c(pool))
     _need_gpu(query_flat, pool, out)
     m, C = query_flat.shape
     n_obj = prep.n_obj
@@ -444,7 +461,7 @@ def dense_match_argmin(query_flat, pool, prep, obj_bias, out, arg, out_pixel_str
     """aoc_dense_match_argmin: dense_match_min's values (bit for bit) and, in ``arg`` (int32, addressed like ``out``), the pool row of every
     minimum; -1 where the winner is a padded distance or nothing is labelled."""
     query_flat = _f32c(query_flat)
-    pool = _f32c(pool)
+    pool = _a16("dense_match_argmin: pool", _f32c(pool))
     _need_gpu(query_flat, pool, out, arg)
     assert arg.dtype == torch.int32
     m, C = query_flat.shape
@@ -626,7 +643,7 @@ def split_record_bytes(C):
 def split_rows(x_flat, out=None, row0=0, overflow=None, tiled=False):
     """x [n, C] fp32 -> SplitRows.  With `out` (a SplitRows with capacity) the records are written at row `row0` of it
     (the reference pool grows in place: only the appended frame is converted).  tiled: tile-major records of the whole x (a query)."""
-    x_flat = _f32c(x_flat)
+    x_flat = _a16("split_rows: x", _f32c(x_flat))
     _need_gpu(x_flat)
     n, C = x_flat.shape
     rb = split_record_bytes(C)
@@ -657,6 +674,7 @@ def split_rows(x_flat, out=None, row0=0, overflow=None, tiled=False):
     sq = out.sqnorm[row0:row0 + n]
     flag = out.overflow
     _out("split_rows: out.records[row0 : row0 + n]", rec, (n, rb), torch.uint8)
+    _a16("split_rows: out.records[row0 : row0 + n]", rec, output=True)
     _out("split_rows: out.sqnorm[row0 : row0 + n]", sq, (n,))
     _span("split_rows: out.overflow", flag, 1, torch.int32)
     _lib.check(_lib.lib().aoc_split_rows(_p(x_flat), n, C, _p(rec), _p(sq), _p(flag), _stream()), "aoc_split_rows")
@@ -676,8 +694,8 @@ def dense_prune_stats(reset=True):
 
 def dense_match_min_split(query_flat, query_split, pool, pool_split, prep, obj_bias, out, out_pixel_stride, out_obj_stride, transform=True):
     """aoc_dense_match_min_split: fp16-split matrix pipe with the exact-fp32 kernels as device-side take-over."""
-    query_flat = _f32c(query_flat)
-    pool = _f32c(pool)
+    query_flat = _a16("dense_match_min_split: query", _f32c(query_flat))
+    pool = _a16("dense_match_min_split: pool", _f32c(pool))
     _need_gpu(query_flat, pool, out, query_split.records, pool_split.records)
     m, C = query_flat.shape
     n_obj = prep.n_obj
@@ -694,7 +712,8 @@ def dense_match_min_split(query_flat, query_split, pool, pool_split, prep, obj_b
     assert not pool_split.tiled
     _span("dense_match_min_split: out", out, _dense_span(m, n_obj, out_pixel_stride, out_obj_stride))
     right_bits, wrong_bits, fg_rows, obj_rows, counts, obj_offsets = _prep_lists(prep)
-    q_rec, q_sq, p_rec = query_split.records, query_split.sqnorm, pool_split.records
+    q_rec, q_sq = _a16("dense_match_min_split: query records", query_split.records), query_split.sqnorm
+    p_rec = _a16("dense_match_min_split: pool records", pool_split.records)
     _lib.check(L.aoc_dense_match_min_split(_p(query_flat), _p(q_rec), _p(q_sq), int(query_split.tiled), m, C, _p(pool),
                                            _p(p_rec),
                                            _p(flag), n, _p(right_bits), _p(wrong_bits), _p(fg_rows), _p(obj_rows),
@@ -768,7 +787,7 @@ def resize_bilinear_planes(x, H, W, out, out_plane_stride, out_pixel_stride, inn
 
 def atrous_subsample(x, rate):
     """aoc_atrous_subsample: [h, w, X] -> [ceil(h / rate), ceil(w / rate), X] = x[::rate, ::rate] (AEM:533-579, the atrous grid of the reference pool)."""
-    x = _f32c(x)
+    x = _a16("atrous_subsample: x", _f32c(x))
     _need_gpu(x)
     h, w, X = x.shape
     rate = int(rate)
@@ -787,7 +806,7 @@ def resize_nearest_bits(bits, h, w, H, W):
 
 def local_window_match(query, prev, right_bits, radii, obj_bias, n_obj, transform=True, atrous_rate=1, float16=False):
     """query, prev [H,W,C] -> [n_obj, len(radii), H, W] (channel order [max, r_0, ...]); atrous_rate / float16 as in the reference call."""
-    query, prev = _f32c(query), _f32c(prev)
+    query, prev = _a16("local_window_match: query", _f32c(query)), _a16("local_window_match: prev", _f32c(prev))
     _need_gpu(query, prev, right_bits)
     right_bits = _i32c(right_bits)
     H, W, C = query.shape
@@ -805,7 +824,7 @@ def local_window_match_argmin(query, prev, right_bits, radii, obj_bias, n_obj, t
     """aoc_local_window_match_argmin: local_window_match's values (float16=False; bit for bit at C = 100 / 128) and, in ``arg`` (int32, shaped
     like ``out``), the previous-frame pixel cy * W + cx of every minimum; -1 where the value is the padding.  -> (out, arg)
     [n_obj, len(radii), H, W].  The keyword buffers, when given, are written in place."""
-    query, prev = _f32c(query), _f32c(prev)
+    query, prev = _a16("local_window_match_argmin: query", _f32c(query)), _a16("local_window_match_argmin: prev", _f32c(prev))
     _need_gpu(query, prev, right_bits, out, arg)
     right_bits = _i32c(right_bits)
     H, W, C = query.shape
@@ -883,7 +902,7 @@ def local_prep(cur_emb, prev_emb, prev_labels_flat, prev_pos, H2, W2, obj_bias=N
 
 def local_window_match_pair(query, prev_a, prev_b, right_bits, radii, obj_bias, n_obj, transform=True):
     """aoc_local_window_match_pair -> [2, n_obj, len(radii), H, W]: local matching against prev_a and prev_b in one launch."""
-    query, prev_a, prev_b = _f32c(query), _f32c(prev_a), _f32c(prev_b)
+    query, prev_a, prev_b = (_a16("local_window_match_pair: " + w, _f32c(t)) for w, t in (("query", query), ("prev_a", prev_a), ("prev_b", prev_b)))
     _need_gpu(query, prev_a, prev_b, right_bits)
     right_bits = _i32c(right_bits)
     H, W, C = query.shape
@@ -976,7 +995,7 @@ def cluster_chain(pool, prep, levels, init_rows, tables, sqnorms, iters=20):
     no host synchronisation).  pool [rows, C]; prep = LabelPrep of the pool's labels; init_rows int32 [F * L * O, kmax]; tables[f] [L*O*2*kmax + O, C],
     sqnorms[f] [L*O*2*kmax + O].  Returns a dict of views into the workspace (centroids, labels, cluster_counts, proxies, proxy_sqnorm, seg_k,
     seg_offsets), valid until the workspace is reused."""
-    pool = _f32c(pool)
+    pool = _a16("cluster_chain: pool", _f32c(pool))
     _need_gpu(pool, init_rows, *tables, *sqnorms)
     F, L, O, C = len(tables), len(levels), prep.n_obj, pool.shape[1]
     kmax = int(max(levels))
@@ -995,6 +1014,7 @@ def cluster_chain(pool, prep, levels, init_rows, tables, sqnorms, iters=20):
         if table.dim() != 2 or table.shape[0] < L * O * 2 * kmax:
             raise ValueError(f"cluster_chain: tables[{f}] {tuple(table.shape)} has fewer than {L * O * 2 * kmax} rows")
         _out(f"cluster_chain: tables[{f}]", table, (table.shape[0], C))
+        _a16(f"cluster_chain: tables[{f}]", table, output=True)
         _span(f"cluster_chain: sqnorms[{f}]", sqn, L * O * 2 * kmax)
         d.tables[f], d.sqnorms[f] = _addr(table), _addr(sqn)
     lib = _lib.lib()
@@ -1125,7 +1145,7 @@ class FrameCall:
             "match_pool takes the contiguous float32 pool [R <= capacity, h, w, C]"
         _need_gpu(ref_emb)
         for r in range(done, R):
-            src, dst = ref_emb[r], self.match_emb[r]
+            src, dst = _a16("FrameCall.match_pool: ref_emb[r]", ref_emb[r]), self.match_emb[r]
             _lib.check(_lib.lib().aoc_atrous_subsample(_p(src), self.h, self.w, self.C, self.grate, _p(dst), _stream()), "aoc_atrous_subsample")
         self.match_frames = R
         labs = torch.stack([atrous_subsample(ref_labels[r], self.grate) for r in range(R)])
@@ -1146,6 +1166,9 @@ class FrameCall:
         right_bits, wrong_bits, fg_rows, obj_rows, counts, obj_offsets = prep.right_bits, prep.wrong_bits, prep.fg_rows, prep.obj_rows, prep.counts, prep.obj_offsets
         for t in (right_bits, wrong_bits, fg_rows, obj_rows, counts, obj_offsets):
             assert t.dtype == torch.int32 and t.is_contiguous(), "aoc_frame_enqueue takes the contiguous int32 lists of ops.label_prep"
+        # class-16 pointers of aoc_frame_desc: the three embeddings are inputs (copied when off the grid), the proxy table is also written
+        ref_emb, prev_emb, cur_emb = _a16("FrameCall: ref_emb", ref_emb), _a16("FrameCall: prev_emb", prev_emb), _a16("FrameCall: cur_emb", cur_emb)
+        _a16("FrameCall: table", table, output=True)
         R = ref_emb.shape[0]
         d = self.desc
         assert R <= self.cap and tuple(cur_emb.shape) == (self.h, self.w, self.C) and ref_labels.shape[-1] == self.n_obj and dis_bias.numel() == self.n_obj

@@ -32,11 +32,12 @@ ERRORS = (TypeError, ValueError, AssertionError)      # + _lib.AocHipError, adde
 
 # ------------------------------------------------------------------------------------------ the recorder and the stub library
 class Record:
-    __slots__ = ("shape", "dtype", "contiguous", "device", "numel", "ref", "alive")
+    __slots__ = ("shape", "dtype", "contiguous", "device", "numel", "ref", "alive", "mod16")
 
 
 class Recorder:
-    """Wraps ops._p and ops._addr: at the moment an address is taken it notes shape, dtype, contiguity, device and a weakref of the tensor.
+    """Wraps ops._p and ops._addr: at the moment an address is taken it notes shape, dtype, contiguity, device, the address modulo 16 (the
+    alignment contract, tests/alignment_cases.py) and a weakref of the tensor.
     The stub library calls entered(): every address taken since the previous library call must still belong to a live tensor THEN."""
 
     def __init__(self):
@@ -48,7 +49,7 @@ class Recorder:
             r.shape = None
         else:
             r.shape, r.dtype, r.contiguous, r.device, r.numel = tuple(t.shape), t.dtype, t.is_contiguous(), t.device, t.numel()
-            r.ref, r.alive = weakref.ref(t), None
+            r.ref, r.alive, r.mod16 = weakref.ref(t), None, t.data_ptr() % 16
             self.pending.append(r)
         self.records.append(r)
 
