@@ -28,6 +28,9 @@ __device__ __forceinline__ float aoc_proto_transform(float d, float bias) {
     float s = 1.0f / (1.0f + expf(-(d + bias)));
     return (s - 0.5f) * 2.0f;
 }
+// ... and its backward from the saved T: grad_out dT/dd = grad_out dT/dbias = (grad_out / 2) (1 - T^2), one product, one difference, one
+// product.  The global, local and cluster matching gradients all gate with THIS routine (their float64 bounds restate it).
+__device__ __forceinline__ float aoc_transform_gate(float grad_out, float T) { return (grad_out * 0.5f) * (1.0f - T * T); }
 
 // single v_min_f32 (fminf would add a canonicalising v_max per operand); operands are never NaN here
 __device__ __forceinline__ float aoc_fmin_raw(float a, float b) {

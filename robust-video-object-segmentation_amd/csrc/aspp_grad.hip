@@ -9,53 +9,21 @@
 //           z, its ReLU mask and cat are recomputed with gn_cat_apply_kernel's own float expression (x a + b, a = rstd gamma, b = beta -
 //           mean a); neither the ungated concatenation nor its gradient is ever stored.
 //
-// A streamed plane is cut as in gate_grad.hip / norm_grad.hip: by the alignment of the plane the pass WRITES (of the gradient plane it reads
-// where nothing is written), up to three scalars in front, 16 bytes per lane for the body, up to three scalars behind; every other operand is
-// accessed 16 bytes per lane through a type that promises 4-byte alignment only.
+// A streamed plane is cut (plane_stream.h) by the alignment of the plane the pass WRITES, or of the gradient plane it reads where nothing is
+// written.
 //
 // No float atomics.  Every sum runs in an order fixed by the shapes and by that alignment cut:
 //   plane sums     aoc_channel_scale_grad's order: thread t of T adds its front scalar, its float4 t, t + T, ... (components .x .y .z .w in
 //                  turn), its back scalar, each product rounded before it is added (-ffp-contract=off); then the xor butterfly of
 //                  aoc_wave_sum; then the wave sums in ascending wave order.  T = 256 for planes of at most 2 048 float4, else 1 024.
-//   small kernels  one thread per output, a serial loop in ascending index of the summed dimension, from 0.0f; the GCT sums over c as in
-//                  gct_gate_grad_kernel.
+//   small kernels  one thread per output, a serial loop in ascending index of the summed dimension, from 0.0f; the GCT sums over c are
+//                  gct_gate_grad_body's (gct_gate_grad.h).
 // The thread counts, the loads in flight and the slices per plane are first choices, not tuned ones.
 #include <stdlib.h>
 
-#include "aoc_common.h"
+#include "gct_gate_grad.h"
 
 namespace {
-
-constexpr int AG_PTR_LIST = 8;
-struct AgSrc { const float *p[AG_PTR_LIST]; };             // host arrays of device pointers travel in the kernel's argument struct
-struct AgDst { float *p[AG_PTR_LIST]; };
-
-typedef f32x4 f32x4_a4 __attribute__((aligned(4)));
-__device__ __forceinline__ f32x4 ag_load4(const float *p) { return *reinterpret_cast<const f32x4_a4 *>(p); }
-__device__ __forceinline__ int64_t ag_front(const void *p, int64_t hw) {
-    const int64_t n = ((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) / 4;
-    return n < hw ? n : hw;
-}
-__device__ __forceinline__ float ag_sign(float v) { return v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f); }
-__device__ __forceinline__ float ag_dot4(float acc, const f32x4 a, const f32x4 b) {
-    acc += a[0] * b[0]; acc += a[1] * b[1]; acc += a[2] * b[2]; acc += a[3] * b[3];
-    return acc;
-}
-// the pointer of set k out of the argument struct without a dynamically indexed private array
-__device__ __forceinline__ const float *ag_pick(const AgSrc &s, int k) {
-    const float *p = s.p[0];
-#pragma unroll
-    for (int j = 1; j < AG_PTR_LIST; ++j)
-        if (k == j) p = s.p[j];
-    return p;
-}
-__device__ __forceinline__ float *ag_pick(const AgDst &s, int k) {
-    float *p = s.p[0];
-#pragma unroll
-    for (int j = 1; j < AG_PTR_LIST; ++j)
-        if (k == j) p = s.p[j];
-    return p;
-}
 
 // ------------------------------------------------------------------------------------------ front 1: dots[k, p] = <g_k[p], x[p]>
 // One workgroup per plane.  Set k's plane is cut by g_k's own alignment (channel_scale_grad_kernel<T, false, true> cuts by grad_y), so set k
@@ -63,58 +31,58 @@ __device__ __forceinline__ float *ag_pick(const AgDst &s, int k) {
 // float4 of x is loaded once and feeds every set's accumulator; otherwise the sets are walked one after the other and x comes from the cache.
 template <int T>
 __device__ __forceinline__ float ag_plane_dot_one(const float *__restrict__ gp, const float *__restrict__ xp, int64_t hw, int t) {
-    const int64_t front = ag_front(gp, hw);
+    const int64_t front = aoc_front(gp, hw);
     const int64_t body4 = (hw - front) / 4, back0 = front + body4 * 4;
     float acc = 0.0f;
     if (t < front) acc += gp[t] * xp[t];
-    for (int64_t i = t; i < body4; i += T) acc = ag_dot4(acc, ag_load4(gp + front + 4 * i), ag_load4(xp + front + 4 * i));
+    for (int64_t i = t; i < body4; i += T) acc = aoc_dot4(acc, aoc_load4(gp + front + 4 * i), aoc_load4(xp + front + 4 * i));
     if (t < hw - back0) acc += gp[back0 + t] * xp[back0 + t];
     return acc;
 }
 
 template <int T>
-__global__ __launch_bounds__(T) void plane_dot_multi_kernel(const float *__restrict__ x, AgSrc g, int n_set, int64_t planes, int64_t hw,
+__global__ __launch_bounds__(T) void plane_dot_multi_kernel(const float *__restrict__ x, AocSrcList g, int n_set, int64_t planes, int64_t hw,
                                                              float *__restrict__ dots) {
-    __shared__ float wsum[AG_PTR_LIST][T / 64];
+    __shared__ float wsum[AOC_PTR_LIST][T / 64];
     const int64_t plane = blockIdx.x;
     const int t = threadIdx.x;
     const float *xp = x + plane * hw;
-    float acc[AG_PTR_LIST];
+    float acc[AOC_PTR_LIST];
 #pragma unroll
-    for (int k = 0; k < AG_PTR_LIST; ++k) acc[k] = 0.0f;
-    const int64_t front = ag_front(g.p[0] + plane * hw, hw);
+    for (int k = 0; k < AOC_PTR_LIST; ++k) acc[k] = 0.0f;
+    const int64_t front = aoc_front(g.p[0] + plane * hw, hw);
     bool same = true;
 #pragma unroll
-    for (int k = 1; k < AG_PTR_LIST; ++k)
-        if (k < n_set) same = same && ag_front(g.p[k] + plane * hw, hw) == front;
+    for (int k = 1; k < AOC_PTR_LIST; ++k)
+        if (k < n_set) same = same && aoc_front(g.p[k] + plane * hw, hw) == front;
     if (same) {
         const int64_t body4 = (hw - front) / 4, back0 = front + body4 * 4;
         if (t < front) {
             const float xv = xp[t];
 #pragma unroll
-            for (int k = 0; k < AG_PTR_LIST; ++k)
+            for (int k = 0; k < AOC_PTR_LIST; ++k)
                 if (k < n_set) acc[k] += g.p[k][plane * hw + t] * xv;
         }
         for (int64_t i = t; i < body4; i += T) {                       // 1 + n_set 16-byte loads in flight per thread
             const int64_t e = plane * hw + front + 4 * i;
-            const f32x4 xv = ag_load4(x + e);
+            const f32x4 xv = aoc_load4(x + e);
 #pragma unroll
-            for (int k = 0; k < AG_PTR_LIST; ++k)
-                if (k < n_set) acc[k] = ag_dot4(acc[k], ag_load4(g.p[k] + e), xv);
+            for (int k = 0; k < AOC_PTR_LIST; ++k)
+                if (k < n_set) acc[k] = aoc_dot4(acc[k], aoc_load4(g.p[k] + e), xv);
         }
         if (t < hw - back0) {
             const float xv = xp[back0 + t];
 #pragma unroll
-            for (int k = 0; k < AG_PTR_LIST; ++k)
+            for (int k = 0; k < AOC_PTR_LIST; ++k)
                 if (k < n_set) acc[k] += g.p[k][plane * hw + back0 + t] * xv;
         }
     } else {
 #pragma unroll
-        for (int k = 0; k < AG_PTR_LIST; ++k)
+        for (int k = 0; k < AOC_PTR_LIST; ++k)
             if (k < n_set) acc[k] = ag_plane_dot_one<T>(g.p[k] + plane * hw, xp, hw, t);
     }
 #pragma unroll
-    for (int k = 0; k < AG_PTR_LIST; ++k) {
+    for (int k = 0; k < AOC_PTR_LIST; ++k) {
         if (k < n_set) {
             const float v = aoc_wave_sum(acc[k]);
             if (aoc_lane() == 0) wsum[k][t >> 6] = v;
@@ -128,60 +96,15 @@ __global__ __launch_bounds__(T) void plane_dot_multi_kernel(const float *__restr
     }
 }
 
-// ------------------------------------------------------------------------------------------ through gct_gate_kernel's expressions
-// The body is a COPY of gct_gate_grad_kernel's (gate_grad.hip), kept line for line, because this file was added without touching that one:
-// the two belong in one __device__ routine called from both (the bit identity of aoc_gct_gate_multi_grad with aoc_gct_gate_grad is tested).
-__device__ __forceinline__ float ag_block_sum256(float v, float *wsum) {
-    v = aoc_wave_sum(v);
-    __syncthreads();                       // wsum may still be read from the previous use
-    if (aoc_lane() == 0) wsum[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-}
-
-__device__ __forceinline__ void ag_gct_gate_grad_body(const float *__restrict__ dgate, const float *__restrict__ gate, const float *__restrict__ s,
-                                                      const float *__restrict__ alpha, const float *__restrict__ gamma, int N, int C, float eps, int l1,
-                                                      float *__restrict__ dsum, float *__restrict__ grad_alpha, float *__restrict__ grad_gamma,
-                                                      float *__restrict__ grad_beta, float *wsum) {
-    for (int n = 0; n < N; ++n) {
-        const size_t row = (size_t)n * C;
-        float pm = 0.0f, pd = 0.0f;
-        for (int c = threadIdx.x; c < C; c += 256) {
-            const float sv = s[row + c];
-            const float e = l1 ? sv * alpha[c] : sqrtf(sv + eps) * alpha[c];
-            const float t = gate[row + c] - 1.0f;
-            const float du = dgate[row + c] * (1.0f - t * t);
-            pm += l1 ? fabsf(e) : e * e;
-            pd += (du * e) * gamma[c];
-        }
-        const float M = ag_block_sum256(pm, wsum) / (float)C;
-        const float num = ag_block_sum256(pd, wsum);
-        const float q = M + eps;
-        const float r = l1 ? q : sqrtf(q);
-        const float dM = l1 ? -num / (q * q) : -0.5f * num / (r * q);
-        for (int c = threadIdx.x; c < C; c += 256) {
-            const float sv = s[row + c];
-            const float root = l1 ? sv : sqrtf(sv + eps);               // de/dalpha
-            const float e = root * alpha[c];
-            const float t = gate[row + c] - 1.0f;
-            const float du = dgate[row + c] * (1.0f - t * t);
-            const float de = l1 ? du * (gamma[c] / r) + ag_sign(e) * dM / (float)C : du * (gamma[c] / r) + 2.0f * e * dM / (float)C;
-            if (dsum) dsum[row + c] = l1 ? de * alpha[c] : de * alpha[c] / (2.0f * root);
-            if (grad_alpha) grad_alpha[c] = (n ? grad_alpha[c] : 0.0f) + de * root;
-            if (grad_gamma) grad_gamma[c] = (n ? grad_gamma[c] : 0.0f) + du * e / r;
-            if (grad_beta) grad_beta[c] = (n ? grad_beta[c] : 0.0f) + du;
-        }
-    }
-}
-
-// front 2: grid (n_set); workgroup k is aoc_gct_gate_grad on row k of the parameters and on dgate[k], gate[k]; all sets read one plane_sums
+// ------------------------------------------------------------------------------------------ front 2: through gct_gate_kernel's expressions
+// grid (n_set); workgroup k is aoc_gct_gate_grad (gct_gate_grad_body) on row k of the parameters and on dgate[k], gate[k]; all sets read one plane_sums
 __global__ __launch_bounds__(256) void gct_gate_multi_grad_kernel(const float *__restrict__ dgate, const float *__restrict__ gate, const float *__restrict__ s,
                                                                   const float *__restrict__ alpha, const float *__restrict__ gamma, int N, int C, float eps,
                                                                   int l1, float *__restrict__ dsum, float *__restrict__ grad_alpha,
                                                                   float *__restrict__ grad_gamma, float *__restrict__ grad_beta) {
     __shared__ float wsum[4];
     const size_t k = blockIdx.x, nc = (size_t)N * C;
-    ag_gct_gate_grad_body(dgate + k * nc, gate + k * nc, s, alpha + k * C, gamma + k * C, N, C, eps, l1, dsum ? dsum + k * nc : nullptr,
+    gct_gate_grad_body(dgate + k * nc, gate + k * nc, s, alpha + k * C, gamma + k * C, N, C, eps, l1, dsum ? dsum + k * nc : nullptr,
                           grad_alpha ? grad_alpha + k * C : nullptr, grad_gamma ? grad_gamma + k * C : nullptr, grad_beta ? grad_beta + k * C : nullptr,
                           wsum);
 }
@@ -198,29 +121,29 @@ __global__ __launch_bounds__(256) void set_sum_kernel(const float *__restrict__ 
 // ------------------------------------------------------------------------------------------ front 3: the apply pass
 // grad_x[p, i] = ((sum_k g_k[p, i] gate_k[p]) + (2 dsum_total[p]) x[p, i]) + dmean[p] / (float)hw: the sum over k starts from the product of
 // set 0 and adds the sets in ascending order; dmean == NULL drops the last addition.  grid (planes, slices), the plane cut by grad_x.
-__device__ __forceinline__ float ag_front_apply1(const float (&gv)[AG_PTR_LIST], const float (&gt)[AG_PTR_LIST], int n_set, float xv, float ds2, float c,
+__device__ __forceinline__ float ag_front_apply1(const float (&gv)[AOC_PTR_LIST], const float (&gt)[AOC_PTR_LIST], int n_set, float xv, float ds2, float c,
                                                  bool has_c) {
     float s = gv[0] * gt[0];
 #pragma unroll
-    for (int k = 1; k < AG_PTR_LIST; ++k)
+    for (int k = 1; k < AOC_PTR_LIST; ++k)
         if (k < n_set) s += gv[k] * gt[k];
     s = s + ds2 * xv;
     return has_c ? s + c : s;
 }
 
-__global__ __launch_bounds__(256) void channel_scale_multi_grad_apply_kernel(AgSrc g, const float *__restrict__ gates, const float *__restrict__ x,
+__global__ __launch_bounds__(256) void channel_scale_multi_grad_apply_kernel(AocSrcList g, const float *__restrict__ gates, const float *__restrict__ x,
                                                                              const float *__restrict__ dsum_total, const float *__restrict__ dmean,
                                                                              int n_set, int64_t planes, int64_t hw, float *__restrict__ grad_x) {
     const int64_t plane = blockIdx.x;                        // planes on x (up to 2^31 - 1), the slices of a plane on y
     const int64_t base = plane * hw;
-    float gt[AG_PTR_LIST];
+    float gt[AOC_PTR_LIST];
 #pragma unroll
-    for (int k = 0; k < AG_PTR_LIST; ++k) gt[k] = k < n_set ? gates[(int64_t)k * planes + plane] : 0.0f;
+    for (int k = 0; k < AOC_PTR_LIST; ++k) gt[k] = k < n_set ? gates[(int64_t)k * planes + plane] : 0.0f;
     const float ds2 = 2.0f * dsum_total[plane];
     const bool has_c = dmean != nullptr;
     const float c = has_c ? dmean[plane] / (float)hw : 0.0f;
     float *op = grad_x + base;
-    const int64_t front = ag_front(op, hw);
+    const int64_t front = aoc_front(op, hw);
     const int64_t body4 = (hw - front) / 4, back0 = front + body4 * 4;
     const int64_t tid = (int64_t)blockIdx.y * 256 + threadIdx.x, nthreads = (int64_t)gridDim.y * 256;
     if (tid < front || tid < hw - back0) {
@@ -228,35 +151,30 @@ __global__ __launch_bounds__(256) void channel_scale_multi_grad_apply_kernel(AgS
         for (int side = 0; side < 2; ++side) {
             const int64_t e = side ? back0 + tid : tid;
             if (side ? tid < hw - back0 : tid < front) {
-                float gv[AG_PTR_LIST];
+                float gv[AOC_PTR_LIST];
 #pragma unroll
-                for (int k = 0; k < AG_PTR_LIST; ++k) gv[k] = k < n_set ? g.p[k][base + e] : 0.0f;
+                for (int k = 0; k < AOC_PTR_LIST; ++k) gv[k] = k < n_set ? g.p[k][base + e] : 0.0f;
                 op[e] = ag_front_apply1(gv, gt, n_set, x[base + e], ds2, c, has_c);
             }
         }
     }
     for (int64_t i = tid; i < body4; i += nthreads) {
         const int64_t e = base + front + 4 * i;
-        f32x4 g4[AG_PTR_LIST];
+        f32x4 g4[AOC_PTR_LIST];
 #pragma unroll
-        for (int k = 0; k < AG_PTR_LIST; ++k)
-            if (k < n_set) g4[k] = ag_load4(g.p[k] + e);
-        const f32x4 x4 = ag_load4(x + e);
+        for (int k = 0; k < AOC_PTR_LIST; ++k)
+            if (k < n_set) g4[k] = aoc_load4(g.p[k] + e);
+        const f32x4 x4 = aoc_load4(x + e);
         f32x4 o;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            float gv[AG_PTR_LIST];
+            float gv[AOC_PTR_LIST];
 #pragma unroll
-            for (int k = 0; k < AG_PTR_LIST; ++k) gv[k] = k < n_set ? g4[k][j] : 0.0f;
+            for (int k = 0; k < AOC_PTR_LIST; ++k) gv[k] = k < n_set ? g4[k][j] : 0.0f;
             o[j] = ag_front_apply1(gv, gt, n_set, x4[j], ds2, c, has_c);
         }
         __builtin_nontemporal_store(o, reinterpret_cast<f32x4 *>(grad_x + e));
     }
-}
-
-inline unsigned ag_apply_blocks(int64_t hw) {
-    const int64_t bx = (hw / 4 + 255) / 256;
-    return (unsigned)(bx < 1 ? 1 : (bx > 8 ? 8 : bx));
 }
 
 // ------------------------------------------------------------------------------------------ back: GroupNorm x n_src -> cat -> GCT
@@ -291,7 +209,7 @@ __device__ __forceinline__ void ag_add1(const AgPlane &P, AgAcc &acc, float gy, 
 // back 1: grid (N * C_total).  A source plane leaves P1 .. P5; a tail plane leaves sum g in P2's slot and P1 = relu(tail) * sum g.  The plane
 // is cut by g's alignment (nothing is written).  P [5][N * C_total].
 template <int T>
-__global__ __launch_bounds__(T) void gn_cat_grad_plane_kernel(const float *__restrict__ g, AgSrc u, int n_src, int N, int C_src, int group_channels,
+__global__ __launch_bounds__(T) void gn_cat_grad_plane_kernel(const float *__restrict__ g, AocSrcList u, int n_src, int N, int C_src, int group_channels,
                                                                int64_t hw, const float *__restrict__ stats, const float *__restrict__ gamma,
                                                                const float *__restrict__ beta, const float *__restrict__ tail, int C_tail,
                                                                float *__restrict__ P) {
@@ -301,22 +219,22 @@ __global__ __launch_bounds__(T) void gn_cat_grad_plane_kernel(const float *__res
     const int n = (int)(plane / C_total), cc = (int)(plane - (int64_t)n * C_total);
     const int t = threadIdx.x;
     const float *gp = g + plane * hw;
-    const int64_t front = ag_front(gp, hw);
+    const int64_t front = aoc_front(gp, hw);
     const int64_t body4 = (hw - front) / 4, back0 = front + body4 * 4;
     const bool is_src = cc < n_src * C_src;
     AgAcc acc = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     if (is_src) {
         const int k = cc / C_src, c = cc - k * C_src;
         const AgPlane Pl = ag_plane(stats, gamma, beta, k, n, c, N, C_src, group_channels);
-        const float *xp = ag_pick(u, k) + ((int64_t)n * C_src + c) * hw;
+        const float *xp = aoc_pick(u, k) + ((int64_t)n * C_src + c) * hw;
         if (t < front) ag_add1(Pl, acc, gp[t], xp[t]);
         int64_t i = t;
         for (; i + (int64_t)T < body4; i += 2 * (int64_t)T) {             // four 16-byte loads in flight per thread
             f32x4 g4[2], x4[2];
 #pragma unroll
             for (int v = 0; v < 2; ++v) {
-                g4[v] = ag_load4(gp + front + 4 * (i + v * (int64_t)T));
-                x4[v] = ag_load4(xp + front + 4 * (i + v * (int64_t)T));
+                g4[v] = aoc_load4(gp + front + 4 * (i + v * (int64_t)T));
+                x4[v] = aoc_load4(xp + front + 4 * (i + v * (int64_t)T));
             }
 #pragma unroll
             for (int v = 0; v < 2; ++v)
@@ -324,7 +242,7 @@ __global__ __launch_bounds__(T) void gn_cat_grad_plane_kernel(const float *__res
                 for (int j = 0; j < 4; ++j) ag_add1(Pl, acc, g4[v][j], x4[v][j]);
         }
         for (; i < body4; i += T) {
-            const f32x4 g4 = ag_load4(gp + front + 4 * i), x4 = ag_load4(xp + front + 4 * i);
+            const f32x4 g4 = aoc_load4(gp + front + 4 * i), x4 = aoc_load4(xp + front + 4 * i);
 #pragma unroll
             for (int j = 0; j < 4; ++j) ag_add1(Pl, acc, g4[j], x4[j]);
         }
@@ -332,7 +250,7 @@ __global__ __launch_bounds__(T) void gn_cat_grad_plane_kernel(const float *__res
     } else {
         if (t < front) acc.p2 += gp[t];
         for (int64_t i = t; i < body4; i += T) {
-            const f32x4 g4 = ag_load4(gp + front + 4 * i);
+            const f32x4 g4 = aoc_load4(gp + front + 4 * i);
             acc.p2 += g4[0]; acc.p2 += g4[1]; acc.p2 += g4[2]; acc.p2 += g4[3];
         }
         if (t < hw - back0) acc.p2 += gp[back0 + t];
@@ -363,7 +281,7 @@ __global__ __launch_bounds__(256) void gn_cat_grad_gate_kernel(const float *__re
                                                                float *__restrict__ ds, float *__restrict__ grad_alpha, float *__restrict__ grad_gamma,
                                                                float *__restrict__ grad_beta) {
     __shared__ float wsum[4];
-    ag_gct_gate_grad_body(P1, gate, s, alpha, gamma, N, C, eps, 0, ds, grad_alpha, grad_gamma, grad_beta, wsum);
+    gct_gate_grad_body(P1, gate, s, alpha, gamma, N, C, eps, 0, ds, grad_alpha, grad_gamma, grad_beta, wsum);
 }
 
 // A[n, cc] = G P2 + (2 ds) P4 and B[n, cc] = G P3 + (2 ds) P5: the same instructions wherever they are needed
@@ -434,13 +352,13 @@ __device__ __forceinline__ float ag_back_apply1(const AgPlane &P, float gg, floa
     return P.rstd * ((P.gam * dz - c1) - xhat * c2);
 }
 
-__global__ __launch_bounds__(256) void gn_cat_grad_apply_kernel(const float *__restrict__ g, AgSrc u, int n_src, int N, int C_src, int C_tail,
+__global__ __launch_bounds__(256) void gn_cat_grad_apply_kernel(const float *__restrict__ g, AocSrcList u, int n_src, int N, int C_src, int C_tail,
                                                                 int group_channels, int64_t hw, const float *__restrict__ stats,
                                                                 const float *__restrict__ gamma, const float *__restrict__ beta, const float *__restrict__ G,
-                                                                const float *__restrict__ ds, const float *__restrict__ coef, AgDst grad_u) {
+                                                                const float *__restrict__ ds, const float *__restrict__ coef, AocDstList grad_u) {
     const int64_t sp = blockIdx.x;                           // (k, n, c)
     const int c = (int)(sp % C_src), n = (int)((sp / C_src) % N), k = (int)(sp / ((int64_t)C_src * N));
-    float *ob = ag_pick(grad_u, k);
+    float *ob = aoc_pick(grad_u, k);
     if (!ob) return;
     const int C_total = n_src * C_src + C_tail;
     const int64_t plane = (int64_t)n * C_total + (int64_t)k * C_src + c;
@@ -449,15 +367,15 @@ __global__ __launch_bounds__(256) void gn_cat_grad_apply_kernel(const float *__r
     const float c1 = coef[2 * gi], c2 = coef[2 * gi + 1];
     const float gg = G[plane], d2 = 2.0f * ds[plane];
     const float *gp = g + plane * hw;
-    const float *xp = ag_pick(u, k) + ((int64_t)n * C_src + c) * hw;
+    const float *xp = aoc_pick(u, k) + ((int64_t)n * C_src + c) * hw;
     float *op = ob + ((int64_t)n * C_src + c) * hw;
-    const int64_t front = ag_front(op, hw);
+    const int64_t front = aoc_front(op, hw);
     const int64_t body4 = (hw - front) / 4, back0 = front + body4 * 4;
     const int64_t tid = (int64_t)blockIdx.y * 256 + threadIdx.x, nthreads = (int64_t)gridDim.y * 256;
     if (tid < front) op[tid] = ag_back_apply1(Pl, gg, d2, c1, c2, gp[tid], xp[tid]);
     for (int64_t i = tid; i < body4; i += nthreads) {
         const int64_t e = front + 4 * i;
-        const f32x4 g4 = ag_load4(gp + e), x4 = ag_load4(xp + e);
+        const f32x4 g4 = aoc_load4(gp + e), x4 = aoc_load4(xp + e);
         f32x4 o;
 #pragma unroll
         for (int j = 0; j < 4; ++j) o[j] = ag_back_apply1(Pl, gg, d2, c1, c2, g4[j], x4[j]);
@@ -506,10 +424,10 @@ inline bool ag_outputs_clash(const AgRange *in, int n_in, const AgRange *out, in
 extern "C" {
 
 int aoc_plane_dot_multi(const float *x, const float *const *g_ptrs, int n_set, int64_t planes, int64_t hw, float *dots, aoc_stream_t stream) {
-    if (!x || !g_ptrs || !dots || n_set < 1 || n_set > AG_PTR_LIST || planes < 1 || hw < 1) return AOC_ERR_INVALID_ARG;
+    if (!x || !g_ptrs || !dots || n_set < 1 || n_set > AOC_PTR_LIST || planes < 1 || hw < 1) return AOC_ERR_INVALID_ARG;
     if (planes > 0x7fffffffLL || hw > INT64_MAX / 4 / planes) return AOC_ERR_UNSUPPORTED;
     const int64_t n = planes * hw;
-    AgSrc g = {};
+    AocSrcList g = {};
     for (int k = 0; k < n_set; ++k) {
         if (!g_ptrs[k]) return AOC_ERR_INVALID_ARG;
         if (ag_overlap(dots, (int64_t)n_set * planes, g_ptrs[k], n)) return AOC_ERR_INVALID_ARG;
@@ -531,7 +449,7 @@ int aoc_gct_gate_multi_grad(const float *dgate, const float *gate, const float *
                             int n_set, int N, int C, float eps, int l1_mode, float *dsum_total, float *dsum, float *grad_alpha, float *grad_gamma,
                             float *grad_beta, void *workspace, size_t workspace_bytes, aoc_stream_t stream) {
     (void)beta;                            // the saved gates carry beta's effect; kept in the signature beside aoc_gct_gate_multi's
-    if (!dgate || !gate || !plane_sums || !alpha || !gamma || n_set < 1 || n_set > AG_PTR_LIST || N < 1 || C < 1) return AOC_ERR_INVALID_ARG;
+    if (!dgate || !gate || !plane_sums || !alpha || !gamma || n_set < 1 || n_set > AOC_PTR_LIST || N < 1 || C < 1) return AOC_ERR_INVALID_ARG;
     if (N > AOC_MAX_OBJECTS) return AOC_ERR_UNSUPPORTED;
     if (!dsum_total && !dsum && !grad_alpha && !grad_gamma && !grad_beta) return AOC_OK;
     const int64_t nc = (int64_t)N * C, snc = (int64_t)n_set * nc, sc = (int64_t)n_set * C;
@@ -554,11 +472,11 @@ int aoc_gct_gate_multi_grad(const float *dgate, const float *gate, const float *
 
 int aoc_channel_scale_multi_grad_apply(const float *const *g_ptrs, const float *gates, const float *x, const float *dsum_total, const float *dmean,
                                        int n_set, int64_t planes, int64_t hw, float *grad_x, aoc_stream_t stream) {
-    if (!g_ptrs || !gates || !x || !dsum_total || !grad_x || n_set < 1 || n_set > AG_PTR_LIST || planes < 1 || hw < 1) return AOC_ERR_INVALID_ARG;
+    if (!g_ptrs || !gates || !x || !dsum_total || !grad_x || n_set < 1 || n_set > AOC_PTR_LIST || planes < 1 || hw < 1) return AOC_ERR_INVALID_ARG;
     if (planes > 0x7fffffffLL || hw > INT64_MAX / 4 / planes) return AOC_ERR_UNSUPPORTED;
     const int64_t n = planes * hw;
-    AgSrc g = {};
-    AgRange in[AG_PTR_LIST + 4];
+    AocSrcList g = {};
+    AgRange in[AOC_PTR_LIST + 4];
     int n_in = 0;
     for (int k = 0; k < n_set; ++k) {
         if (!g_ptrs[k]) return AOC_ERR_INVALID_ARG;
@@ -571,14 +489,14 @@ int aoc_channel_scale_multi_grad_apply(const float *const *g_ptrs, const float *
     in[n_in++] = {dmean, planes};
     const AgRange out[] = {{grad_x, n}};
     if (ag_outputs_clash(in, n_in, out, 1)) return AOC_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(channel_scale_multi_grad_apply_kernel, dim3((unsigned)planes, ag_apply_blocks(hw)), dim3(256), 0, aoc_hip_stream(stream), g, gates, x,
+    hipLaunchKernelGGL(channel_scale_multi_grad_apply_kernel, dim3((unsigned)planes, aoc_plane_slices(hw)), dim3(256), 0, aoc_hip_stream(stream), g, gates, x,
                        dsum_total, dmean, n_set, planes, hw, grad_x);
     AOC_RETURN_IF_LAUNCH_FAILED();
     return AOC_OK;
 }
 
 size_t aoc_groupnorm_cat_relu_grad_workspace_bytes(int n_src, int N, int C_src, int C_tail, int groups) {
-    if (n_src < 1 || n_src > AG_PTR_LIST || N < 1 || C_src < 1 || C_tail < 0 || groups < 1 || C_src % groups) return 0;
+    if (n_src < 1 || n_src > AOC_PTR_LIST || N < 1 || C_src < 1 || C_tail < 0 || groups < 1 || C_src % groups) return 0;
     return ag_carve(nullptr, n_src, N, C_src, C_tail, groups).total;
 }
 
@@ -587,7 +505,7 @@ int aoc_groupnorm_cat_relu_grad(const float *grad_out, const float *const *u_ptr
                                 const float *gct_alpha, const float *gct_gamma, float gct_eps, float *const *grad_u_ptrs, float *grad_gamma,
                                 float *grad_beta, float *grad_tail, float *grad_gct_alpha, float *grad_gct_gamma, float *grad_gct_beta, void *workspace,
                                 size_t workspace_bytes, aoc_stream_t stream) {
-    if (!grad_out || !u_ptrs || !stats || !plane_sumsq || !gate || !gct_alpha || !gct_gamma || n_src < 1 || n_src > AG_PTR_LIST || N < 1 || C_src < 1 ||
+    if (!grad_out || !u_ptrs || !stats || !plane_sumsq || !gate || !gct_alpha || !gct_gamma || n_src < 1 || n_src > AOC_PTR_LIST || N < 1 || C_src < 1 ||
         hw < 1 || groups < 1 || C_tail < 0)
         return AOC_ERR_INVALID_ARG;
     if (C_src % groups) return AOC_ERR_INVALID_ARG;
@@ -598,9 +516,9 @@ int aoc_groupnorm_cat_relu_grad(const float *grad_out, const float *const *u_ptr
     if (hw > INT64_MAX / 4 / ((int64_t)N * C_total)) return AOC_ERR_UNSUPPORTED;
     const int64_t planes = (int64_t)N * C_total, ny = planes * hw, nx = (int64_t)N * C_src * hw, n_aff = (int64_t)n_src * C_src;
     const int64_t n_stats = (int64_t)n_src * N * groups * 2;
-    AgSrc u = {};
-    AgDst gu = {};
-    AgRange in[AG_PTR_LIST + 10], out[AG_PTR_LIST + 8];
+    AocSrcList u = {};
+    AocDstList gu = {};
+    AgRange in[AOC_PTR_LIST + 10], out[AOC_PTR_LIST + 8];
     int n_in = 0, n_out = 0;
     bool any_u = false;
     for (int k = 0; k < n_src; ++k) {
@@ -651,7 +569,7 @@ int aoc_groupnorm_cat_relu_grad(const float *grad_out, const float *const *u_ptr
                            grad_beta, grad_tail);
     }
     if (any_u)
-        hipLaunchKernelGGL(gn_cat_grad_apply_kernel, dim3((unsigned)((int64_t)n_src * N * C_src), ag_apply_blocks(hw)), dim3(256), 0, st, grad_out, u, n_src, N,
+        hipLaunchKernelGGL(gn_cat_grad_apply_kernel, dim3((unsigned)((int64_t)n_src * N * C_src), aoc_plane_slices(hw)), dim3(256), 0, st, grad_out, u, n_src, N,
                            C_src, C_tail, gc, hw, stats, gamma, beta, gate, (const float *)w.ds, (const float *)w.coef, gu);
     AOC_RETURN_IF_LAUNCH_FAILED();
     return AOC_OK;

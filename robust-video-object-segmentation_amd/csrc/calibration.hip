@@ -3,7 +3,7 @@
 // All of them are HBM-bound: one coalesced pass over the big operand, reductions in LDS/registers.
 #include <stdlib.h>
 
-#include "aoc_common.h"
+#include "plane_stream.h"
 
 namespace {
 
@@ -357,7 +357,6 @@ __device__ __forceinline__ float film_gain_wg256(const float *__restrict__ h, co
 template <int U>
 __global__ __launch_bounds__(256) void film_scale_ahead_kernel(const float *__restrict__ x, const float *__restrict__ head, const float *__restrict__ weight,
                                                                 const float *__restrict__ bias, int D, int channels, int64_t hw, int chunk, float *__restrict__ y) {
-    typedef float f32x4_t __attribute__((ext_vector_type(4)));
     __shared__ float wsum[4];
     const int64_t plane = blockIdx.y;
     const int o = (int)(plane / channels), c = (int)(plane - (int64_t)o * channels);
@@ -368,10 +367,10 @@ __global__ __launch_bounds__(256) void film_scale_ahead_kernel(const float *__re
     if (headn > hw) headn = hw;
     const int64_t body4 = (hw - headn) / 4;
     const bool vec = ((reinterpret_cast<uintptr_t>(yp) & 15) == (addr & 15)) && body4 > 0;
-    const f32x4_t *x4 = reinterpret_cast<const f32x4_t *>(xp + headn);
+    const f32x4 *x4 = reinterpret_cast<const f32x4 *>(xp + headn);
     // the plane's float4 split evenly over the workgroups of the row (the last one is not a mostly empty straggler)
     const int64_t i0 = (int64_t)blockIdx.x * chunk, i1 = min(body4, i0 + chunk);          // chunk = ceil((hw / 4) / gridDim.x) <= 256 U
-    f32x4_t v[U];
+    f32x4 v[U];
     if (vec) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -381,7 +380,7 @@ __global__ __launch_bounds__(256) void film_scale_ahead_kernel(const float *__re
     }
     const float g = film_gain_wg256(head + (size_t)o * D, weight + (size_t)c * D, bias, c, D, wsum);
     if (vec) {
-        f32x4_t *y4 = reinterpret_cast<f32x4_t *>(yp + headn);
+        f32x4 *y4 = reinterpret_cast<f32x4 *>(yp + headn);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int64_t i = i0 + threadIdx.x + u * 256;
@@ -398,17 +397,9 @@ __global__ __launch_bounds__(256) void film_scale_ahead_kernel(const float *__re
 }
 
 // ---- streams whose source and destination planes may sit at different 16-byte misalignments ------------------------------------------
-// The plane is cut by the DESTINATION's alignment: up to three scalar floats in front, 16-byte non-temporal stores for the body, up to three
-// scalars behind.  Every source is loaded 16 bytes per lane through a vector type that promises the compiler 4-byte alignment only: one
-// global_load_dwordx4 whether the source plane sits at the destination's misalignment or at another one (with odd hw consecutive planes
-// alternate their misalignment, and three base pointers need not agree).  Nothing falls back to a scalar plane.
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef f32x4_t f32x4_a4_t __attribute__((aligned(4)));
-__device__ __forceinline__ f32x4_t stream_load4(const float *p) { return __builtin_nontemporal_load(reinterpret_cast<const f32x4_a4_t *>(p)); }
-__device__ __forceinline__ int64_t floats_to_alignment(const void *p, int64_t hw) {
-    const int64_t n = ((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) / 4;
-    return n < hw ? n : hw;
-}
+// The plane is cut (plane_stream.h) by the DESTINATION's alignment, the body stored with 16-byte non-temporal stores; every source is loaded
+// with aoc_stream_load4 whether its plane sits at the destination's misalignment or at another one (with odd hw consecutive planes alternate
+// their misalignment, and three base pointers need not agree).  Nothing falls back to a scalar plane.
 
 // torch.cat([x, mem], 1) + IA_gate (decoding_module.py:193-194, :203-204) in one launch, modelled on film_scale_ahead_kernel: grid.y = plane
 // of y; the plane's source is a plane of x (c < Cx) or of mem; the workgroup's slice is requested before the dot product.  x and mem may be
@@ -423,16 +414,16 @@ __global__ __launch_bounds__(256) void cat_film_scale_kernel(const float *x, con
     const int o = (int)(plane / C), c = (int)(plane - (int64_t)o * C);
     const float *sp = c < Cx ? x + ((int64_t)o * Cx + c) * hw : mem + ((int64_t)o * Cm + (c - Cx)) * hw;
     float *yp = y + plane * hw;
-    const int64_t headn = floats_to_alignment(yp, hw);
+    const int64_t headn = aoc_front(yp, hw);
     const int64_t body4 = (hw - headn) / 4;
     const int64_t i0 = (int64_t)blockIdx.x * chunk, i1 = min(body4, i0 + chunk);          // chunk = ceil((hw / 4) / gridDim.x) <= 256 U
     const bool vec = i0 < i1;
-    f32x4_t v[U];
+    f32x4 v[U];
     if (vec) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int64_t i = i0 + threadIdx.x + u * 256;
-            if (i < i1) v[u] = stream_load4(sp + headn + 4 * i);
+            if (i < i1) v[u] = aoc_stream_load4(sp + headn + 4 * i);
         }
     }
     const int64_t tail0 = headn + body4 * 4;
@@ -446,7 +437,7 @@ __global__ __launch_bounds__(256) void cat_film_scale_kernel(const float *x, con
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int64_t i = i0 + threadIdx.x + u * 256;
-            if (i < i1) __builtin_nontemporal_store(v[u] * g, reinterpret_cast<f32x4_t *>(yp + headn + 4 * i));
+            if (i < i1) __builtin_nontemporal_store(v[u] * g, reinterpret_cast<f32x4 *>(yp + headn + 4 * i));
         }
     }
     if (has_edge) yp[e] = g * edge;
@@ -731,8 +722,10 @@ __global__ __launch_bounds__(256) void cond_masked_gap_fused_kernel(const float 
 // GroupNorm as torch computes it (biased variance over the group's channels x HW), then y = relu(gn(x) [+ residual]).  PyTorch runs the
 // normalisation, the residual add and the ReLU as separate passes; here x is read twice (statistics, apply) and y written once.
 // Statistics: per (sample, group) block, per-thread fp32 partial sums of x and x^2 folded in fp64 (fixed order: reproducible).
-__global__ __launch_bounds__(256) void gn_stats_kernel(const float *__restrict__ x, int group_channels, int64_t hw, float eps,
-                                                        float *__restrict__ stats /* [N * groups][2] mean, rstd */) {
+// gn_stats_body: workgroup blockIdx.x of 256 threads on group blockIdx.x of x.  The single-tensor and the multi-tensor entry both run it, and
+// the GroupNorm gradients recompute z from these stats: the order of the sums is part of the result.
+__device__ __forceinline__ void gn_stats_body(const float *__restrict__ x, int group_channels, int64_t hw, float eps,
+                                              float *__restrict__ stats /* [N * groups][2] mean, rstd */) {
     __shared__ double sh[2][4];
     const float *xp = x + (size_t)blockIdx.x * group_channels * hw;
     const int64_t n = (int64_t)group_channels * hw;
@@ -759,6 +752,10 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float *__restrict__
         stats[2 * blockIdx.x] = (float)mean;
         stats[2 * blockIdx.x + 1] = (float)(1.0 / sqrt(var + (double)eps));
     }
+}
+
+__global__ __launch_bounds__(256) void gn_stats_kernel(const float *__restrict__ x, int group_channels, int64_t hw, float eps, float *__restrict__ stats) {
+    gn_stats_body(x, group_channels, hw, eps, stats);
 }
 
 // grid (ceil(hw / 1024), N * C): y = [relu]( (x - mean) * rstd * gamma[c] + beta[c] [+ residual] )
@@ -798,18 +795,18 @@ __global__ __launch_bounds__(256) void gn_apply_scale_kernel(const float *x, int
     const float *xp = x + (size_t)plane * hw;
     const float *rp = residual ? residual + (size_t)plane * hw : nullptr;
     float *yp = y + (size_t)plane * hw;
-    const int64_t headn = floats_to_alignment(yp, hw);
+    const int64_t headn = aoc_front(yp, hw);
     const int64_t body4 = (hw - headn) / 4;
     const int64_t i0 = (int64_t)blockIdx.x * chunk, i1 = min(body4, i0 + chunk);
     const bool vec = i0 < i1;
-    f32x4_t v[U], r[U];
+    f32x4 v[U], r[U];
     if (vec) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int64_t i = i0 + threadIdx.x + u * 256;
             if (i < i1) {
-                v[u] = stream_load4(xp + headn + 4 * i);
-                if (rp) r[u] = stream_load4(rp + headn + 4 * i);
+                v[u] = aoc_stream_load4(xp + headn + 4 * i);
+                if (rp) r[u] = aoc_stream_load4(rp + headn + 4 * i);
             }
         }
     }
@@ -826,10 +823,10 @@ __global__ __launch_bounds__(256) void gn_apply_scale_kernel(const float *x, int
         for (int u = 0; u < U; ++u) {
             const int64_t i = i0 + threadIdx.x + u * 256;
             if (i < i1) {
-                f32x4_t t = v[u] * a + b;
+                f32x4 t = v[u] * a + b;
                 if (rp) t += r[u];
                 if (relu) { t.x = fmaxf(t.x, 0.0f); t.y = fmaxf(t.y, 0.0f); t.z = fmaxf(t.z, 0.0f); t.w = fmaxf(t.w, 0.0f); }
-                __builtin_nontemporal_store(t * g, reinterpret_cast<f32x4_t *>(yp + headn + 4 * i));
+                __builtin_nontemporal_store(t * g, reinterpret_cast<f32x4 *>(yp + headn + 4 * i));
             }
         }
     }
@@ -866,18 +863,17 @@ __global__ __launch_bounds__(64) void linear_kernel(const float *__restrict__ x,
 // float4 loads, eight per thread in flight (32 KB per workgroup: one workgroup per plane, 4-8 workgroups per CU, needs that much outstanding to
 // reach the HBM rate); the 16-byte aligned body + scalar head / tail of the streaming kernels (hw is odd for the 16k + 1 input sizes)
 __global__ __launch_bounds__(256) void plane_mean4_kernel(const float *__restrict__ x, int64_t hw, float *__restrict__ out) {
-    typedef float f32x4_t __attribute__((ext_vector_type(4)));
     __shared__ float wsum[4];
     const float *xp = x + (size_t)blockIdx.x * hw;
     int64_t headn = ((16 - (reinterpret_cast<uintptr_t>(xp) & 15)) & 15) / 4;
     if (headn > hw) headn = hw;
     const int64_t body4 = (hw - headn) / 4, tail0 = headn + body4 * 4;
-    const f32x4_t *x4 = reinterpret_cast<const f32x4_t *>(xp + headn);
+    const f32x4 *x4 = reinterpret_cast<const f32x4 *>(xp + headn);
     float acc = 0.0f;
     if (threadIdx.x < headn) acc += xp[threadIdx.x];
     if (threadIdx.x < hw - tail0) acc += xp[tail0 + threadIdx.x];
     for (int64_t i0 = threadIdx.x; i0 < body4; i0 += 8 * 256) {
-        f32x4_t v[8];
+        f32x4 v[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int64_t i = i0 + u * 256;
@@ -940,8 +936,11 @@ __global__ __launch_bounds__(256) void plane_reduce_kernel(const float *__restri
 //   l2: e_c = sqrt(s_c + eps) * alpha_c,  norm_c = gamma_c / sqrt(mean_c(e_c^2) + eps)
 //   l1: e_c = s_c * alpha_c,              norm_c = gamma_c / (mean_c|e_c| + eps)
 //   gate[n, c] = 1 + tanh(e_c * norm_c + beta_c)
-__global__ __launch_bounds__(256) void gct_gate_kernel(const float *__restrict__ s, const float *__restrict__ alpha, const float *__restrict__ gamma,
-                                                       const float *__restrict__ beta, int C, float eps, int l1, float *__restrict__ gate) {
+// gct_gate_body: workgroup blockIdx.x on sample blockIdx.x of one parameter set.  The single-set and the multi-set entry both run it, and the
+// gradient (gct_gate_grad.h) recomputes e and the mean with these expressions: per thread ascending c, aoc_wave_sum, the four wave sums as
+// (0 + 1) + (2 + 3).
+__device__ __forceinline__ void gct_gate_body(const float *__restrict__ s, const float *__restrict__ alpha, const float *__restrict__ gamma,
+                                              const float *__restrict__ beta, int C, float eps, int l1, float *__restrict__ gate) {
     __shared__ float wsum[4];
     __shared__ float mean_s;
     const int n = blockIdx.x;
@@ -963,6 +962,11 @@ __global__ __launch_bounds__(256) void gct_gate_kernel(const float *__restrict__
         const float norm = l1 ? gamma[c] / (m + eps) : gamma[c] / sqrtf(m + eps);
         gate[(size_t)n * C + c] = 1.0f + tanhf(e * norm + beta[c]);
     }
+}
+
+__global__ __launch_bounds__(256) void gct_gate_kernel(const float *__restrict__ s, const float *__restrict__ alpha, const float *__restrict__ gamma,
+                                                       const float *__restrict__ beta, int C, float eps, int l1, float *__restrict__ gate) {
+    gct_gate_body(s, alpha, gamma, beta, C, eps, l1, gate);
 }
 
 // IA_logit (decoding_module.py:151-160): logit[n, p] = sum_c x[n, c, p] * weight[n, c] + bias[n]: a 1x1 grouped convolution
@@ -1126,24 +1130,20 @@ __global__ __launch_bounds__(PH_PIX) void prehead_apply_kernel(const float *__re
 // ASPP (networks/layers/aspp.py:7-70): the statistics its four branch GCTs and its pooled branch share, the four gated copies of its input in
 // one pass, and the four GroupNorm + ReLU with the concatenation (and the plane norms of GCT(640)) in two.  Per element the expressions are
 // those of plane_reduce_kernel / plane_mean4_kernel, gct_gate_kernel, channel_scale_kernel, gn_stats_kernel and gn_apply_kernel.
-constexpr int AOC_PTR_LIST = 8;
-struct SrcList { const float *p[AOC_PTR_LIST]; };          // host arrays of device pointers travel in the kernel's argument struct
-struct DstList { float *p[AOC_PTR_LIST]; };
-
 // One pass over a plane: sum of x, sum of x^2 and the mean (aspp.py:19 via gct.py:19, four times, and aspp.py:46).  One workgroup per plane,
 // the traversal of plane_mean4_kernel (aligned float4 body, scalar head and tail, eight loads in flight); a fixed order, no atomics.
 __global__ __launch_bounds__(256) void plane_sum_sumsq_kernel(const float *__restrict__ x, int64_t hw, float *__restrict__ sum, float *__restrict__ sumsq,
                                                                float *__restrict__ mean) {
     __shared__ float wsum[2][4];
     const float *xp = x + (size_t)blockIdx.x * hw;
-    const int64_t headn = floats_to_alignment(xp, hw);
+    const int64_t headn = aoc_front(xp, hw);
     const int64_t body4 = (hw - headn) / 4, tail0 = headn + body4 * 4;
-    const f32x4_t *x4 = reinterpret_cast<const f32x4_t *>(xp + headn);
+    const f32x4 *x4 = reinterpret_cast<const f32x4 *>(xp + headn);
     float s = 0.0f, q = 0.0f;
     if (threadIdx.x < headn) { const float v = xp[threadIdx.x]; s += v; q += v * v; }
     if (threadIdx.x < hw - tail0) { const float v = xp[tail0 + threadIdx.x]; s += v; q += v * v; }
     for (int64_t i0 = threadIdx.x; i0 < body4; i0 += 8 * 256) {
-        f32x4_t v[8];
+        f32x4 v[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int64_t i = i0 + u * 256;
@@ -1169,35 +1169,13 @@ __global__ __launch_bounds__(256) void plane_sum_sumsq_kernel(const float *__res
     }
 }
 
-// gct_gate_kernel for n_sets parameter sets over ONE [N, C] array of plane sums (aspp1..4.GCT read the same x): grid (N, n_sets), the body of
-// gct_gate_kernel on set blockIdx.y's alpha / gamma / beta, so each set carries the bits of aoc_gct_gate.  gate [n_sets, N, C].
-// The body is a COPY of gct_gate_kernel's, kept line for line, only because this kernel was added without touching the existing one: the two
-// belong in one __device__ routine called from both (test_gct_gate_multi_bits fails as soon as they drift apart).
+// gct_gate_kernel for n_sets parameter sets over ONE [N, C] array of plane sums (aspp1..4.GCT read the same x): grid (N, n_sets), gct_gate_body
+// on set blockIdx.y's alpha / gamma / beta, so each set carries the bits of aoc_gct_gate.  gate [n_sets, N, C].
 __global__ __launch_bounds__(256) void gct_gate_multi_kernel(const float *__restrict__ s, const float *__restrict__ alpha_all, const float *__restrict__ gamma_all,
                                                               const float *__restrict__ beta_all, int C, float eps, int l1, float *__restrict__ gate_all) {
-    __shared__ float wsum[4];
-    __shared__ float mean_s;
-    const int n = blockIdx.x, N = gridDim.x;
-    const float *alpha = alpha_all + (size_t)blockIdx.y * C, *gamma = gamma_all + (size_t)blockIdx.y * C, *beta = beta_all + (size_t)blockIdx.y * C;
-    float *gate = gate_all + (size_t)blockIdx.y * N * C;
-    float part = 0.0f;
-    for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        const float sv = s[(size_t)n * C + c];
-        const float e = l1 ? sv * alpha[c] : sqrtf(sv + eps) * alpha[c];
-        part += l1 ? fabsf(e) : e * e;
-    }
-    part = aoc_wave_sum(part);
-    if (aoc_lane() == 0) wsum[threadIdx.x >> 6] = part;
-    __syncthreads();
-    if (threadIdx.x == 0) mean_s = ((wsum[0] + wsum[1]) + (wsum[2] + wsum[3])) / (float)C;
-    __syncthreads();
-    const float m = mean_s;
-    for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        const float sv = s[(size_t)n * C + c];
-        const float e = l1 ? sv * alpha[c] : sqrtf(sv + eps) * alpha[c];
-        const float norm = l1 ? gamma[c] / (m + eps) : gamma[c] / sqrtf(m + eps);
-        gate[(size_t)n * C + c] = 1.0f + tanhf(e * norm + beta[c]);
-    }
+    const size_t set = blockIdx.y;
+    const int N = gridDim.x;
+    gct_gate_body(s, alpha_all + set * C, gamma_all + set * C, beta_all + set * C, C, eps, l1, gate_all + set * N * C);
 }
 
 // y_k[p, :] = gains[k, p] * x[p, :] for k < n_out: x is read once for all its gated copies (aspp.py:19 via gct.py:36, four times).  grid.y =
@@ -1206,18 +1184,18 @@ __global__ __launch_bounds__(256) void gct_gate_multi_kernel(const float *__rest
 // exactly the elements it loaded.  Four float4 per thread: with eight the compiler keeps the products of every output live (208 VGPRs).
 constexpr int CSM_U = 4;
 __global__ __launch_bounds__(256) void channel_scale_multi_kernel(const float *x, const float *__restrict__ gains, int n_out, int64_t planes, int64_t hw,
-                                                                   int chunk, DstList y) {
+                                                                   int chunk, AocDstList y) {
     constexpr int U = CSM_U;
     const int64_t plane = blockIdx.y;
     const float *xp = x + plane * hw;
-    const int64_t headn = floats_to_alignment(y.p[0] + plane * hw, hw);
+    const int64_t headn = aoc_front(y.p[0] + plane * hw, hw);
     const int64_t body4 = (hw - headn) / 4;
     const int64_t i0 = (int64_t)blockIdx.x * chunk, i1 = min(body4, i0 + chunk);          // chunk = ceil((hw / 4) / gridDim.x) <= 256 U
-    f32x4_t v[U];
+    f32x4 v[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const int64_t i = i0 + threadIdx.x + u * 256;
-        if (i < i1) v[u] = stream_load4(xp + headn + 4 * i);
+        if (i < i1) v[u] = aoc_stream_load4(xp + headn + 4 * i);
     }
     const int64_t tail0 = headn + body4 * 4;
     const int64_t e = threadIdx.x < headn ? threadIdx.x : tail0 + (threadIdx.x - headn);
@@ -1232,49 +1210,16 @@ __global__ __launch_bounds__(256) void channel_scale_multi_kernel(const float *x
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int64_t i = i0 + threadIdx.x + u * 256;
-                if (i < i1) __builtin_nontemporal_store(v[u] * g, reinterpret_cast<f32x4_a4_t *>(yp + headn + 4 * i));
+                if (i < i1) __builtin_nontemporal_store(v[u] * g, reinterpret_cast<f32x4_a4 *>(yp + headn + 4 * i));
             }
             if (has_edge) yp[e] = g * edge;
         }
     }
 }
 
-// gn_stats_kernel over n_src tensors in one launch: grid (N * groups, n_src), the routine of gn_stats_kernel on source blockIdx.y
-// (per-thread fp32 partial sums of 8 folded in fp64, fixed order); stats [n_src][N * groups][2].  As above, the body is a line-for-line COPY
-// of gn_stats_kernel's for the same reason and should become one __device__ routine shared by both (test_groupnorm_cat_relu_bits_and_plane_sumsq
-// compares the bits of the two).
-__global__ __launch_bounds__(256) void gn_stats_multi_kernel(SrcList src, int group_channels, int64_t hw, float eps, float *__restrict__ stats_all) {
-    __shared__ double sh[2][4];
-    const float *x = src.p[0];
-#pragma unroll
-    for (int k = 1; k < AOC_PTR_LIST; ++k)
-        if ((int)blockIdx.y == k) x = src.p[k];
-    float *stats = stats_all + (size_t)blockIdx.y * gridDim.x * 2;
-    const float *xp = x + (size_t)blockIdx.x * group_channels * hw;
-    const int64_t n = (int64_t)group_channels * hw;
-    double s = 0.0, q = 0.0;
-    int64_t i = threadIdx.x;
-    for (; i + 7 * 256 < n; i += 8 * 256) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = xp[i + u * 256];
-        float ps = 0.f, pq = 0.f;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) { ps += v[u]; pq += v[u] * v[u]; }
-        s += ps; q += pq;
-    }
-    for (; i < n; i += 256) { const float v = xp[i]; s += v; q += (double)v * v; }
-    for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); q += __shfl_xor(q, o); }
-    if (aoc_lane() == 0) { sh[0][threadIdx.x >> 6] = s; sh[1][threadIdx.x >> 6] = q; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const double ts = (sh[0][0] + sh[0][1]) + (sh[0][2] + sh[0][3]), tq = (sh[1][0] + sh[1][1]) + (sh[1][2] + sh[1][3]);
-        const double mean = ts / (double)n;
-        double var = tq / (double)n - mean * mean;
-        if (var < 0.0) var = 0.0;
-        stats[2 * blockIdx.x] = (float)mean;
-        stats[2 * blockIdx.x + 1] = (float)(1.0 / sqrt(var + (double)eps));
-    }
+// gn_stats_kernel over n_src tensors in one launch: grid (N * groups, n_src), gn_stats_body on source blockIdx.y; stats [n_src][N * groups][2]
+__global__ __launch_bounds__(256) void gn_stats_multi_kernel(AocSrcList src, int group_channels, int64_t hw, float eps, float *__restrict__ stats_all) {
+    gn_stats_body(aoc_pick(src, (int)blockIdx.y), group_channels, hw, eps, stats_all + (size_t)blockIdx.y * gridDim.x * 2);
 }
 
 // The apply pass of n_src GroupNorms written straight into their concatenation (aspp.py:21-23 four times, :62-63): one workgroup per plane of
@@ -1283,7 +1228,7 @@ __global__ __launch_bounds__(256) void gn_stats_multi_kernel(SrcList src, int gr
 // y's alignment, sources are loaded 16 bytes per lane at any misalignment.  plane_sumsq (optional) = the sum over the plane of the squares of
 // the values being stored (what GCT(640) would read the concatenation for, aspp.py:65), in a fixed order.
 template <int U>
-__global__ __launch_bounds__(256) void gn_cat_apply_kernel(SrcList src, int n_src, int N, int C_src, int group_channels, int64_t hw,
+__global__ __launch_bounds__(256) void gn_cat_apply_kernel(AocSrcList src, int n_src, int N, int C_src, int group_channels, int64_t hw,
                                                             const float *__restrict__ stats, const float *__restrict__ gamma, const float *__restrict__ beta,
                                                             const float *__restrict__ tail, int C_tail, int relu, float *__restrict__ y,
                                                             float *__restrict__ plane_sumsq) {
@@ -1292,17 +1237,14 @@ __global__ __launch_bounds__(256) void gn_cat_apply_kernel(SrcList src, int n_sr
     const int64_t plane = blockIdx.x;
     const int n = (int)(plane / C_total), cc = (int)(plane - (int64_t)n * C_total);
     float *yp = y + plane * hw;
-    const int64_t headn = floats_to_alignment(yp, hw);
+    const int64_t headn = aoc_front(yp, hw);
     const int64_t body4 = (hw - headn) / 4, tail0 = headn + body4 * 4;
     const int64_t e = threadIdx.x < headn ? threadIdx.x : tail0 + (threadIdx.x - headn);
     const bool has_edge = e < hw && (threadIdx.x < headn || e >= tail0);
     float acc = 0.0f;
     if (cc < n_src * C_src) {
         const int k = cc / C_src, c = cc - k * C_src;
-        const float *xk = src.p[0];
-#pragma unroll
-        for (int j = 1; j < AOC_PTR_LIST; ++j)
-            if (k == j) xk = src.p[j];
+        const float *xk = aoc_pick(src, k);
         const int groups = C_src / group_channels;
         const int g = (k * N + n) * groups + c / group_channels;
         const float mean = stats[2 * g], rstd = stats[2 * g + 1];
@@ -1315,19 +1257,19 @@ __global__ __launch_bounds__(256) void gn_cat_apply_kernel(SrcList src, int n_sr
             acc += t * t;
         }
         for (int64_t i0 = threadIdx.x; i0 < body4; i0 += U * 256) {
-            f32x4_t v[U];
+            f32x4 v[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int64_t i = i0 + u * 256;
-                v[u] = stream_load4(xp + headn + 4 * (i < body4 ? i : body4 - 1));
+                v[u] = aoc_stream_load4(xp + headn + 4 * (i < body4 ? i : body4 - 1));
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int64_t i = i0 + u * 256;
                 if (i < body4) {
-                    f32x4_t t = v[u] * a + b;
+                    f32x4 t = v[u] * a + b;
                     if (relu) { t.x = fmaxf(t.x, 0.0f); t.y = fmaxf(t.y, 0.0f); t.z = fmaxf(t.z, 0.0f); t.w = fmaxf(t.w, 0.0f); }
-                    __builtin_nontemporal_store(t, reinterpret_cast<f32x4_t *>(yp + headn + 4 * i));
+                    __builtin_nontemporal_store(t, reinterpret_cast<f32x4 *>(yp + headn + 4 * i));
                     acc += (t.x * t.x + t.y * t.y) + (t.z * t.z + t.w * t.w);
                 }
             }
@@ -1335,10 +1277,10 @@ __global__ __launch_bounds__(256) void gn_cat_apply_kernel(SrcList src, int n_sr
     } else {
         float t = tail[(size_t)n * C_tail + (cc - n_src * C_src)];
         if (relu) t = fmaxf(t, 0.0f);
-        const f32x4_t t4 = {t, t, t, t};
+        const f32x4 t4 = {t, t, t, t};
         if (has_edge) { yp[e] = t; acc += t * t; }
         for (int64_t i = threadIdx.x; i < body4; i += 256) {
-            __builtin_nontemporal_store(t4, reinterpret_cast<f32x4_t *>(yp + headn + 4 * i));
+            __builtin_nontemporal_store(t4, reinterpret_cast<f32x4 *>(yp + headn + 4 * i));
             acc += (t * t + t * t) + (t * t + t * t);
         }
     }
@@ -1710,7 +1652,7 @@ int aoc_channel_scale_multi(const float *x, const float *gains, int n_out, int64
     if (planes > 65535) return AOC_ERR_UNSUPPORTED;
     if (hw > INT64_MAX / 4 / planes) return AOC_ERR_UNSUPPORTED;
     const int64_t n = planes * hw;
-    DstList dst = {};
+    AocDstList dst = {};
     for (int k = 0; k < n_out; ++k) {
         float *yk = y_ptrs[k];
         if (!yk) return AOC_ERR_INVALID_ARG;
@@ -1743,7 +1685,7 @@ int aoc_groupnorm_cat_relu(const float *const *x_ptrs, int n_src, int N, int C_s
     if (C_total > 2147483647ll || (int64_t)N * C_total > 2147483647ll || (int64_t)N * groups > 2147483647ll) return AOC_ERR_UNSUPPORTED;
     if (hw > INT64_MAX / 4 / ((int64_t)N * C_total)) return AOC_ERR_UNSUPPORTED;
     const int64_t ny = (int64_t)N * C_total * hw, nx = (int64_t)N * C_src * hw;
-    SrcList src = {};
+    AocSrcList src = {};
     for (int k = 0; k < n_src; ++k) {
         if (!x_ptrs[k]) return AOC_ERR_INVALID_ARG;
         if (ranges_overlap(y, ny, x_ptrs[k], nx)) return AOC_ERR_INVALID_ARG;              // y aliases no input

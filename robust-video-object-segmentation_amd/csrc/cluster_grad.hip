@@ -1,10 +1,10 @@
 // Training-time cluster matching (AEM:405-478 over AEM:231-332): the set minimum of aoc_proxy_corr_min with the winner's slot, the
 // backward of that minimum and the pull-back of the gradient through centroid_avg (AEM:280) to the reference embeddings.
 //
-// The forward repeats proxy_corr_min_kernel's arithmetic term by term (correlation.hip: the same v_mfma_f32_16x16x4_f32 sequence over the
-// channels 4t + kq, |q|^2 as four strided partial sums folded by two lane exchanges, |p|^2 as given or summed stream after stream,
-// d = (|q|^2 + |p|^2) - 2 q.p), so its values equal aoc_proxy_corr_min's bit for bit; the proxies are read from global memory (a few
-// KB that stay in cache) and a slot index rides beside each lane's running minimum.  correlation.hip is untouched.
+// The forward keeps proxy_corr_min_kernel's arithmetic (correlation.hip: the same v_mfma_f32_16x16x4_f32 sequence over the channels
+// 4t + kq, |q|^2 as four strided partial sums folded by two lane exchanges, |p|^2 as given or summed stream after stream,
+// d = (|q|^2 + |p|^2) - 2 q.p), so its values equal aoc_proxy_corr_min's bit for bit (tested); the proxies are read from global memory (a
+// few KB that stay in cache) and a slot index rides beside each lane's running minimum.
 //
 // The backward is the inverse of the dense case: few rows, every one of them hot.  Stage 1 cuts the pixels into a fixed number of
 // contiguous chunks; a workgroup owns (chunk, set, group of 32 slots), walks its pixels in order and adds g q_i into the LDS row of the
@@ -35,7 +35,7 @@ inline int cg_chunks(int64_t m) {
 }
 
 // ------------------------------------------------------------------------------------------ forward
-// load_a_fragment of correlation.hip (fp32 mode), term by term
+// the A fragment (16 query rows) and the rows' squared norms in fp32; correlation.hip's load_a_fragment carries the float16 rounding as well
 template <int TMAX>
 __device__ __forceinline__ void cg_load_a(const float *__restrict__ query, int64_t m, int C, int64_t row0, float (&a)[TMAX], float &q2) {
     const int lane = aoc_lane();
@@ -126,8 +126,6 @@ __global__ __launch_bounds__(256) void cg_set_argmin_kernel(const float *__restr
 }
 
 // ------------------------------------------------------------------------------------------ backward of the set minimum
-__device__ __forceinline__ float cg_gate(float go, float t) { return (go * 0.5f) * (1.0f - t * t); }
-
 // one wave per pixel; lane handles channels lane, lane + 64, ...
 __global__ __launch_bounds__(256) void cg_query_grad_kernel(const float *__restrict__ grad_out, const float *__restrict__ T, const int32_t *__restrict__ arg,
                                                             int64_t pstride, const float *__restrict__ query, int64_t m, int C,
@@ -146,7 +144,7 @@ __global__ __launch_bounds__(256) void cg_query_grad_kernel(const float *__restr
         const int64_t at = i * pstride + sets.off[s];
         const int a = arg[at];
         if (a < 0 || a >= sets.size[s]) continue;
-        const float g2 = 2.0f * cg_gate(grad_out[at], T[at]);
+        const float g2 = 2.0f * aoc_transform_gate(grad_out[at], T[at]);
         const float *p = proxies + (size_t)(sets.begin[s] + a) * C;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -182,7 +180,7 @@ __global__ __launch_bounds__(256) void cg_partial_kernel(const float *__restrict
         const int64_t at = i * pstride + off;
         const int a = arg[at] - slot0;
         if (a < 0 || a >= ns) continue;
-        const float g = cg_gate(grad_out[at], T[at]);
+        const float g = aoc_transform_gate(grad_out[at], T[at]);
         if (c < C) cg_lds[a * C + c] += g * query[i * C + c];
         if (c == 0) sumg[a] += g;
     }

@@ -2,10 +2,9 @@
 // (CLB:24-86).  Six entry points (include/aoc_hip.h); aoc_amd.gates_train wires them into autograd.
 //
 // Three of them stream activation-sized tensors (channel_scale_grad, gct_scale_grad, cond_scale_grad); the other three work on the small
-// [N, C] / [C, D] operands.  A streamed plane is cut by the alignment of the plane it WRITES (or, for the plane dot that writes nothing,
-// of grad_y): up to three scalar floats in front, 16 bytes per lane for the body, up to three scalars behind.  Every source is loaded
-// 16 bytes per lane through a vector type that promises 4-byte alignment only, so a source plane may sit at another misalignment than the
-// destination (scores [N, hw] against the planes [N, C, hw] with odd hw) without falling back to a scalar plane.
+// [N, C] / [C, D] operands.  A streamed plane is cut (plane_stream.h) by the alignment of the plane it WRITES, or, for the plane dot that
+// writes nothing, of grad_y; a source plane may sit at another misalignment than the destination (scores [N, hw] against the planes
+// [N, C, hw] with odd hw) without falling back to a scalar plane.
 //
 // No float atomics.  Every sum runs in an order fixed by the shapes and by that alignment cut:
 //   plane dot      thread t of T adds its front scalar, its float4 t, t + T, ... (components .x .y .z .w in turn), its back scalar, each
@@ -14,21 +13,9 @@
 //   small kernels  one thread per output, a serial loop in ascending index of the summed dimension, from 0.0f.
 #include <stdlib.h>
 
-#include "aoc_common.h"
+#include "gct_gate_grad.h"
 
 namespace {
-
-typedef f32x4 f32x4_a4 __attribute__((aligned(4)));
-__device__ __forceinline__ f32x4 gg_load4(const float *p) { return *reinterpret_cast<const f32x4_a4 *>(p); }
-__device__ __forceinline__ int64_t gg_front(const void *p, int64_t hw) {
-    const int64_t n = ((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) / 4;
-    return n < hw ? n : hw;
-}
-__device__ __forceinline__ float gg_sign(float v) { return v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f); }      // torch.sign: sign(0) = 0
-__device__ __forceinline__ float gg_dot4(float acc, const f32x4 a, const f32x4 b) {
-    acc += a[0] * b[0]; acc += a[1] * b[1]; acc += a[2] * b[2]; acc += a[3] * b[3];
-    return acc;
-}
 
 // ------------------------------------------------------------------------------------------ 1: grad_x = gain * grad_y, dgain = <grad_y, x>
 // One workgroup per plane; grad_y and x are read once, grad_x written once.  WRITE / DOT select the halves at compile time.
@@ -42,7 +29,7 @@ __global__ __launch_bounds__(T) void channel_scale_grad_kernel(const float *__re
     const float *xp = DOT ? x + plane * hw : nullptr;
     float *op = WRITE ? gx + plane * hw : nullptr;
     const float g = WRITE ? gain[plane] : 0.0f;
-    const int64_t front = gg_front(WRITE ? (const void *)op : (const void *)gp, hw);
+    const int64_t front = aoc_front(WRITE ? (const void *)op : (const void *)gp, hw);
     const int64_t body4 = (hw - front) / 4, back0 = front + body4 * 4;
     float acc = 0.0f;
     if (t < front) {
@@ -57,18 +44,18 @@ __global__ __launch_bounds__(T) void channel_scale_grad_kernel(const float *__re
         f32x4 a[4], b[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            a[u] = gg_load4(gb + 4 * (i + u * (int64_t)T));
-            if (DOT) b[u] = gg_load4(xb + 4 * (i + u * (int64_t)T));
+            a[u] = aoc_load4(gb + 4 * (i + u * (int64_t)T));
+            if (DOT) b[u] = aoc_load4(xb + 4 * (i + u * (int64_t)T));
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            if (DOT) acc = gg_dot4(acc, a[u], b[u]);
+            if (DOT) acc = aoc_dot4(acc, a[u], b[u]);
             if (WRITE) __builtin_nontemporal_store(a[u] * g, reinterpret_cast<f32x4 *>(op + front) + (i + u * (int64_t)T));
         }
     }
     for (; i < body4; i += T) {
-        const f32x4 a = gg_load4(gb + 4 * i);
-        if (DOT) acc = gg_dot4(acc, a, gg_load4(xb + 4 * i));
+        const f32x4 a = aoc_load4(gb + 4 * i);
+        if (DOT) acc = aoc_dot4(acc, a, aoc_load4(xb + 4 * i));
         if (WRITE) __builtin_nontemporal_store(a * g, reinterpret_cast<f32x4 *>(op + front) + i);
     }
     if (t < hw - back0) {
@@ -152,52 +139,13 @@ __global__ __launch_bounds__(256) void film_gain_grad_kernel(const float *__rest
 }
 
 // ------------------------------------------------------------------------------------------ 3: through gct_gate_kernel's expressions
-// One workgroup walks the samples n in ascending order; the thread that owns channel c adds sample n's term to the three parameter
-// gradients of c (a plain read-modify-write of its own element: no other thread touches it).  The two sums over c per sample (M and the
-// dM numerator) are block sums: per thread ascending c, aoc_wave_sum, the four wave sums as (0 + 1) + (2 + 3).
-__device__ __forceinline__ float gg_block_sum256(float v, float *wsum) {
-    v = aoc_wave_sum(v);
-    __syncthreads();                       // wsum may still be read from the previous use
-    if (aoc_lane() == 0) wsum[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-}
-
+// one workgroup: gct_gate_grad_body (gct_gate_grad.h)
 __global__ __launch_bounds__(256) void gct_gate_grad_kernel(const float *__restrict__ dgate, const float *__restrict__ gate, const float *__restrict__ s,
                                                             const float *__restrict__ alpha, const float *__restrict__ gamma, int N, int C, float eps, int l1,
                                                             float *__restrict__ dsum, float *__restrict__ grad_alpha, float *__restrict__ grad_gamma,
                                                             float *__restrict__ grad_beta) {
     __shared__ float wsum[4];
-    for (int n = 0; n < N; ++n) {
-        const size_t row = (size_t)n * C;
-        float pm = 0.0f, pd = 0.0f;
-        for (int c = threadIdx.x; c < C; c += 256) {
-            const float sv = s[row + c];
-            const float e = l1 ? sv * alpha[c] : sqrtf(sv + eps) * alpha[c];
-            const float t = gate[row + c] - 1.0f;
-            const float du = dgate[row + c] * (1.0f - t * t);
-            pm += l1 ? fabsf(e) : e * e;
-            pd += (du * e) * gamma[c];
-        }
-        const float M = gg_block_sum256(pm, wsum) / (float)C;
-        const float num = gg_block_sum256(pd, wsum);
-        // l2: norm = gamma / r, r = sqrt(M + eps), dM = -1/2 num / (r (M + eps));   l1: norm = gamma / q, q = M + eps, dM = -num / q^2
-        const float q = M + eps;
-        const float r = l1 ? q : sqrtf(q);
-        const float dM = l1 ? -num / (q * q) : -0.5f * num / (r * q);
-        for (int c = threadIdx.x; c < C; c += 256) {
-            const float sv = s[row + c];
-            const float root = l1 ? sv : sqrtf(sv + eps);               // de/dalpha
-            const float e = root * alpha[c];
-            const float t = gate[row + c] - 1.0f;
-            const float du = dgate[row + c] * (1.0f - t * t);
-            const float de = l1 ? du * (gamma[c] / r) + gg_sign(e) * dM / (float)C : du * (gamma[c] / r) + 2.0f * e * dM / (float)C;
-            if (dsum) dsum[row + c] = l1 ? de * alpha[c] : de * alpha[c] / (2.0f * root);
-            if (grad_alpha) grad_alpha[c] = (n ? grad_alpha[c] : 0.0f) + de * root;
-            if (grad_gamma) grad_gamma[c] = (n ? grad_gamma[c] : 0.0f) + du * e / r;
-            if (grad_beta) grad_beta[c] = (n ? grad_beta[c] : 0.0f) + du;
-        }
-    }
+    gct_gate_grad_body(dgate, gate, s, alpha, gamma, N, C, eps, l1, dsum, grad_alpha, grad_gamma, grad_beta, wsum);
 }
 
 // ------------------------------------------------------------------------------------------ 4, 6: the apply passes
@@ -205,7 +153,7 @@ __global__ __launch_bounds__(256) void gct_gate_grad_kernel(const float *__restr
 // KIND 1 (conditioning): out = (gy * a[plane] + (scores[n, p] > thr[n] ? b[plane] / hw : 0)) + c[plane] / hw;  gy == NULL drops the first term
 template <int KIND>
 __device__ __forceinline__ float gg_apply1(float gyv, float sv, float a, float b, float c, float thr, int mode, bool has_gy) {
-    if (KIND == 0) return gyv * a + b * (mode == 1 ? 2.0f * sv : (mode == 2 ? gg_sign(sv) : 1.0f));
+    if (KIND == 0) return gyv * a + b * (mode == 1 ? 2.0f * sv : (mode == 2 ? aoc_sign(sv) : 1.0f));
     const float m = sv > thr ? b : 0.0f;
     return (has_gy ? gyv * a + m : m) + c;
 }
@@ -224,24 +172,19 @@ __global__ __launch_bounds__(256) void gate_apply_kernel(const float *__restrict
     const float b = pb ? pb[plane] / div : 0.0f;
     const float c = (KIND == 1 && pc) ? pc[plane] / div : 0.0f;
     const float thr = KIND == 1 ? thr_all[srow] : 0.0f;
-    const int64_t front = gg_front(op, hw);
+    const int64_t front = aoc_front(op, hw);
     const int64_t body4 = (hw - front) / 4, back0 = front + body4 * 4;
     const int64_t tid = (int64_t)blockIdx.y * 256 + threadIdx.x, nthreads = (int64_t)gridDim.y * 256;
     if (tid < front) op[tid] = gg_apply1<KIND>(has_gy ? gp[tid] : 0.0f, sp[tid], a, b, c, thr, mode, has_gy);
     for (int64_t i = tid; i < body4; i += nthreads) {
-        const f32x4 sv = gg_load4(sp + front + 4 * i);
+        const f32x4 sv = aoc_load4(sp + front + 4 * i);
         f32x4 gv = {0.0f, 0.0f, 0.0f, 0.0f}, o;
-        if (has_gy) gv = gg_load4(gp + front + 4 * i);
+        if (has_gy) gv = aoc_load4(gp + front + 4 * i);
 #pragma unroll
         for (int k = 0; k < 4; ++k) o[k] = gg_apply1<KIND>(gv[k], sv[k], a, b, c, thr, mode, has_gy);
         __builtin_nontemporal_store(o, reinterpret_cast<f32x4 *>(op + front) + i);
     }
     if (tid < hw - back0) op[back0 + tid] = gg_apply1<KIND>(has_gy ? gp[back0 + tid] : 0.0f, sp[back0 + tid], a, b, c, thr, mode, has_gy);
-}
-
-inline unsigned gg_apply_blocks(int64_t hw) {
-    const int64_t bx = (hw / 4 + 255) / 256;
-    return (unsigned)(bx < 1 ? 1 : (bx > 8 ? 8 : bx));
 }
 
 // ------------------------------------------------------------------------------------------ 5: through cond_codes_kernel
@@ -344,7 +287,7 @@ int aoc_gct_scale_grad(const float *grad_y, const float *x, const float *gate, c
                        aoc_stream_t stream) {
     if (!grad_y || !x || !gate || !dsum || !grad_x || planes < 1 || hw < 1 || mode < 0 || mode > 2) return AOC_ERR_INVALID_ARG;
     if (planes > 0x7fffffffLL) return AOC_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(gate_apply_kernel<0>, dim3((unsigned)planes, gg_apply_blocks(hw)), dim3(256), 0, aoc_hip_stream(stream), grad_y, x, (int64_t)1, gate,
+    hipLaunchKernelGGL(gate_apply_kernel<0>, dim3((unsigned)planes, aoc_plane_slices(hw)), dim3(256), 0, aoc_hip_stream(stream), grad_y, x, (int64_t)1, gate,
                        dsum, (const float *)nullptr, (const float *)nullptr, 1.0f, mode, hw, grad_x);
     AOC_RETURN_IF_LAUNCH_FAILED();
     return AOC_OK;
@@ -370,7 +313,7 @@ int aoc_cond_scale_grad(const float *grad_y, const float *gain, const float *sco
                         int C, int64_t hw, float *grad_x, aoc_stream_t stream) {
     if (!scores || !threshold || !grad_x || N < 1 || C < 1 || hw < 1 || (grad_y && !gain)) return AOC_ERR_INVALID_ARG;
     if (N > AOC_MAX_OBJECTS || (int64_t)N * C > 0x7fffffffLL) return AOC_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(gate_apply_kernel<1>, dim3((unsigned)((int64_t)N * C), gg_apply_blocks(hw)), dim3(256), 0, aoc_hip_stream(stream), grad_y, scores, (int64_t)C,
+    hipLaunchKernelGGL(gate_apply_kernel<1>, dim3((unsigned)((int64_t)N * C), aoc_plane_slices(hw)), dim3(256), 0, aoc_hip_stream(stream), grad_y, scores, (int64_t)C,
                        gain, dgap, dpx, threshold, (float)hw, 0, hw, grad_x);
     AOC_RETURN_IF_LAUNCH_FAILED();
     return AOC_OK;

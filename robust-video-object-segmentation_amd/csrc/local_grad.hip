@@ -6,7 +6,7 @@
 // the previous frame into [HW, C, (2R+1)^2] and keeps that and the masked distance volume for autograd; here the backward needs the
 // winning pixel per (object, channel, query pixel), the saved T and the two maps.
 //
-//   g[o, ch, i]   = (grad_out * 0.5f) * (1.0f - T * T)                                  mg_gate's expression (match_grad.hip)
+//   g[o, ch, i]   = (grad_out * 0.5f) * (1.0f - T * T)                                  aoc_transform_gate (aoc_common.h)
 //   grad_query[i] = sum over (o, ch), ascending, of (2 g) * (q_i - p_arg)               a gather
 //   grad_prev[j]  = sum over the (i, o, ch) with arg = j, ascending i, then o, then ch, of (2 g) * (p_j - q_i)
 //                   also a gather: only query pixels within the window of j can have chosen it, so a workgroup per previous-frame
@@ -258,8 +258,6 @@ __global__ __launch_bounds__(256) void lg_window_argmin_kernel(const float *__re
 }
 
 // ------------------------------------------------------------------------------------------ backward
-__device__ __forceinline__ float lg_gate(float grad_out, float T) { return (grad_out * 0.5f) * (1.0f - T * T); }   // mg_gate
-
 // g and a checked copy of arg, pixel-major [i][o * n_radii + ch] for the two gathers (an arg outside the map or the window becomes -1,
 // its g zero)
 __global__ __launch_bounds__(256) void lg_gate_kernel(const float *__restrict__ grad_out, const float *__restrict__ T, const int32_t *__restrict__ arg,
@@ -277,7 +275,7 @@ __global__ __launch_bounds__(256) void lg_gate_kernel(const float *__restrict__ 
         dx = dx < 0 ? -dx : dx;
         ok = dy <= window && dx <= window;
     }
-    gbuf[(int64_t)i * P + p] = ok ? lg_gate(grad_out[idx], T[idx]) : 0.0f;
+    gbuf[(int64_t)i * P + p] = ok ? aoc_transform_gate(grad_out[idx], T[idx]) : 0.0f;
     abuf[(int64_t)i * P + p] = ok ? a : -1;
 }
 

@@ -27,8 +27,6 @@ inline __host__ __device__ int mg_stage_rows(int C) { return C > 128 ? MG_CHUNK 
 constexpr int MG_BIAS_PIX = 256;   // pixels per first-stage block of the bias sum
 constexpr int PG_PIX = 64;         // pixels per first-stage block of the proxy sums
 
-__device__ __forceinline__ float mg_gate(float grad_out, float T) { return (grad_out * 0.5f) * (1.0f - T * T); }
-
 // One wave per pixel: g and a bounds-checked dense copy of arg for the later kernels, the pairs counted per pool row, grad_query.
 __global__ __launch_bounds__(64) void mg_pairs_kernel(const float *__restrict__ grad_out, const float *__restrict__ T, const int32_t *__restrict__ arg,
                                                       int64_t pstride, int64_t ostride, const float *__restrict__ query,
@@ -41,7 +39,7 @@ __global__ __launch_bounds__(64) void mg_pairs_kernel(const float *__restrict__ 
     const int lane = threadIdx.x;
     if (lane < n_obj) {
         const int64_t at = i * pstride + lane * ostride;
-        const float g = mg_gate(grad_out[at], T[at]);
+        const float g = aoc_transform_gate(grad_out[at], T[at]);
         int32_t a = arg[at];
         if (a < 0 || a >= n) a = -1;
         gbuf[i * n_obj + lane] = g;
@@ -198,7 +196,7 @@ __global__ __launch_bounds__(64) void pg_pairs_kernel(const float *__restrict__ 
     const int lane = threadIdx.x;
     if (lane < n_obj) {
         const int64_t at = i * pstride + lane * ostride;
-        const float g = mg_gate(grad_out[at], T[at]);
+        const float g = aoc_transform_gate(grad_out[at], T[at]);
         gbuf[i * n_obj + lane] = g;
         lg[lane] = g;
     }

@@ -6,31 +6,18 @@
 // A = sum dz, B = sum dz xhat and dgain = sum grad_y a), one small launch (the group sums s1 / M, s2 / M, grad_gamma, grad_beta) and an
 // apply pass (the same three streams again, grad_x and grad_residual written once).  z is recomputed with the forward's expression
 // (x a + b, then + residual, with gn_apply_kernel's a and b), so the mask z > 0 is the one the forward's fmaxf applied; no xhat, mask,
-// grad_y a product or ungated activation is ever stored.  A streamed plane is cut as in gate_grad.hip: by the alignment of the plane the
-// pass WRITES (grad_x, else grad_residual; of grad_y where nothing is written), up to three scalars in front, 16 bytes per lane for the
-// body, up to three scalars behind; sources, and a second destination, are accessed 16 bytes per lane at 4-byte alignment.
+// grad_y a product or ungated activation is ever stored.  A streamed plane is cut (plane_stream.h) by the alignment of the plane the
+// pass WRITES (grad_x, else grad_residual; of grad_y where nothing is written); sources, and a second destination, are accessed 16 bytes
+// per lane at 4-byte alignment.
 //
 // No float atomics.  Every sum runs in an order fixed by the shapes and by that alignment cut:
 //   plane sums     aoc_channel_scale_grad's order: thread t of T adds its front scalar, its float4 t, t + T, ... (components .x .y .z .w in
 //                  turn), its back scalar, each product rounded before it is added (-ffp-contract=off); then the xor butterfly of
 //                  aoc_wave_sum; then the wave sums in ascending wave order.  T = 256 for planes of at most 2 048 float4, else 1 024.
 //   small kernel   one thread per output, a serial loop in ascending index of the summed dimension, from 0.0f.
-#include "aoc_common.h"
+#include "plane_stream.h"
 
 namespace {
-
-typedef f32x4 f32x4_a4 __attribute__((aligned(4)));
-__device__ __forceinline__ f32x4 ng_load4(const float *p) { return *reinterpret_cast<const f32x4_a4 *>(p); }
-__device__ __forceinline__ void ng_store4_a4(float *p, const f32x4 v) { *reinterpret_cast<f32x4_a4 *>(p) = v; }
-// 16 bytes per lane to a destination that shares the cut's alignment (nontemporal: a pure stream-out), else at 4-byte alignment
-__device__ __forceinline__ void ng_store4(float *p, const f32x4 v, bool aligned16) {
-    if (aligned16) __builtin_nontemporal_store(v, reinterpret_cast<f32x4 *>(p));
-    else ng_store4_a4(p, v);
-}
-__device__ __forceinline__ int64_t ng_front(const void *p, int64_t hw) {
-    const int64_t n = ((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) / 4;
-    return n < hw ? n : hw;
-}
 
 // what a plane's elements need of the forward: z = x a + b [+ r] (gn_apply_kernel's expression), xhat = (x - mean) rstd
 struct NgPlane {
@@ -89,7 +76,7 @@ __global__ __launch_bounds__(T) void gn_grad_plane_kernel(const float *__restric
     const float *xp = x + plane * hw;
     const bool has_r = res != nullptr;
     const float *rp = has_r ? res + plane * hw : nullptr;
-    const int64_t front = ng_front(gp, hw);
+    const int64_t front = aoc_front(gp, hw);
     const int64_t body4 = (hw - front) / 4, back0 = front + body4 * 4;
     NgAcc acc = {0.0f, 0.0f, 0.0f};
     if (t < front) ng_add1(P, acc, gp[t], xp[t], has_r ? rp[t] : 0.0f, has_r);
@@ -98,9 +85,9 @@ __global__ __launch_bounds__(T) void gn_grad_plane_kernel(const float *__restric
         f32x4 g4[2], x4[2], r4[2];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
-            g4[u] = ng_load4(gp + front + 4 * (i + u * (int64_t)T));
-            x4[u] = ng_load4(xp + front + 4 * (i + u * (int64_t)T));
-            if (has_r) r4[u] = ng_load4(rp + front + 4 * (i + u * (int64_t)T));
+            g4[u] = aoc_load4(gp + front + 4 * (i + u * (int64_t)T));
+            x4[u] = aoc_load4(xp + front + 4 * (i + u * (int64_t)T));
+            if (has_r) r4[u] = aoc_load4(rp + front + 4 * (i + u * (int64_t)T));
         }
 #pragma unroll
         for (int u = 0; u < 2; ++u)
@@ -108,9 +95,9 @@ __global__ __launch_bounds__(T) void gn_grad_plane_kernel(const float *__restric
             for (int k = 0; k < 4; ++k) ng_add1(P, acc, g4[u][k], x4[u][k], has_r ? r4[u][k] : 0.0f, has_r);
     }
     for (; i < body4; i += T) {
-        const f32x4 g4 = ng_load4(gp + front + 4 * i), x4 = ng_load4(xp + front + 4 * i);
+        const f32x4 g4 = aoc_load4(gp + front + 4 * i), x4 = aoc_load4(xp + front + 4 * i);
         f32x4 r4 = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (has_r) r4 = ng_load4(rp + front + 4 * i);
+        if (has_r) r4 = aoc_load4(rp + front + 4 * i);
 #pragma unroll
         for (int k = 0; k < 4; ++k) ng_add1(P, acc, g4[k], x4[k], r4[k], has_r);
     }
@@ -189,7 +176,7 @@ __global__ __launch_bounds__(256) void gn_grad_apply_kernel(const float *__restr
     const float *rp = has_r ? res + plane * hw : nullptr;
     float *ox = grad_x ? grad_x + plane * hw : nullptr;
     float *orr = grad_res ? grad_res + plane * hw : nullptr;
-    const int64_t front = ng_front(ox ? ox : orr, hw);
+    const int64_t front = aoc_front(ox ? ox : orr, hw);
     const int64_t body4 = (hw - front) / 4, back0 = front + body4 * 4;
     const int64_t tid = (int64_t)blockIdx.y * 256 + threadIdx.x, nthreads = (int64_t)gridDim.y * 256;
     if (tid < front) {
@@ -200,9 +187,9 @@ __global__ __launch_bounds__(256) void gn_grad_apply_kernel(const float *__restr
     }
     for (int64_t i = tid; i < body4; i += nthreads) {
         const int64_t e = front + 4 * i;
-        const f32x4 g4 = ng_load4(gp + e), x4 = ng_load4(xp + e);
+        const f32x4 g4 = aoc_load4(gp + e), x4 = aoc_load4(xp + e);
         f32x4 r4 = {0.0f, 0.0f, 0.0f, 0.0f}, vx, vr;
-        if (has_r) r4 = ng_load4(rp + e);
+        if (has_r) r4 = aoc_load4(rp + e);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             float a, b;
@@ -212,7 +199,7 @@ __global__ __launch_bounds__(256) void gn_grad_apply_kernel(const float *__restr
         }
         if (ox) {
             __builtin_nontemporal_store(vx, reinterpret_cast<f32x4 *>(ox + e));
-            if (orr) ng_store4_a4(orr + e, vr);              // the second destination may sit at another misalignment
+            if (orr) aoc_store4_a4(orr + e, vr);              // the second destination may sit at another misalignment
         } else {
             __builtin_nontemporal_store(vr, reinterpret_cast<f32x4 *>(orr + e));
         }
@@ -224,11 +211,6 @@ __global__ __launch_bounds__(256) void gn_grad_apply_kernel(const float *__restr
         if (ox) ox[e] = vx;
         if (orr) orr[e] = vr;
     }
-}
-
-inline unsigned ng_apply_blocks(int64_t hw) {
-    const int64_t bx = (hw / 4 + 255) / 256;
-    return (unsigned)(bx < 1 ? 1 : (bx > 8 ? 8 : bx));
 }
 
 struct NgWs {
@@ -267,7 +249,7 @@ __global__ __launch_bounds__(T) void cat_scale_grad_kernel(const float *__restri
     float *op = c < Cx ? (grad_x ? grad_x + (o * Cx + c) * hw : nullptr) : (grad_mem ? grad_mem + (o * Cm + (c - Cx)) * hw : nullptr);
     const bool dot = dgain != nullptr;
     const float g = op ? gain[plane] : 0.0f;
-    const int64_t front = ng_front(gp, hw);                   // always grad_y's cut: dgain's bits do not depend on what else is written
+    const int64_t front = aoc_front(gp, hw);                   // always grad_y's cut: dgain's bits do not depend on what else is written
     const int64_t body4 = (hw - front) / 4, back0 = front + body4 * 4;
     const bool op16 = op && ((reinterpret_cast<uintptr_t>(op + front) & 15) == 0);
     float acc = 0.0f;
@@ -281,22 +263,22 @@ __global__ __launch_bounds__(T) void cat_scale_grad_kernel(const float *__restri
         f32x4 a[4], b[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            a[u] = ng_load4(gp + front + 4 * (i + u * (int64_t)T));
-            if (dot) b[u] = ng_load4(sp + front + 4 * (i + u * (int64_t)T));
+            a[u] = aoc_load4(gp + front + 4 * (i + u * (int64_t)T));
+            if (dot) b[u] = aoc_load4(sp + front + 4 * (i + u * (int64_t)T));
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             if (dot) { acc += a[u][0] * b[u][0]; acc += a[u][1] * b[u][1]; acc += a[u][2] * b[u][2]; acc += a[u][3] * b[u][3]; }
-            if (op) ng_store4(op + front + 4 * (i + u * (int64_t)T), a[u] * g, op16);
+            if (op) aoc_store4(op + front + 4 * (i + u * (int64_t)T), a[u] * g, op16);
         }
     }
     for (; i < body4; i += T) {
-        const f32x4 a = ng_load4(gp + front + 4 * i);
+        const f32x4 a = aoc_load4(gp + front + 4 * i);
         if (dot) {
-            const f32x4 b = ng_load4(sp + front + 4 * i);
+            const f32x4 b = aoc_load4(sp + front + 4 * i);
             acc += a[0] * b[0]; acc += a[1] * b[1]; acc += a[2] * b[2]; acc += a[3] * b[3];
         }
-        if (op) ng_store4(op + front + 4 * i, a * g, op16);
+        if (op) aoc_store4(op + front + 4 * i, a * g, op16);
     }
     if (t < hw - back0) {
         const float v = gp[back0 + t];
@@ -351,7 +333,7 @@ int aoc_groupnorm_relu_grad(const float *grad_y, const float *x, const float *re
                            (float)((int64_t)gc * hw), grad_x ? w.coef : (float *)nullptr, grad_gamma, grad_beta);
     }
     if (grad_x || grad_residual)
-        hipLaunchKernelGGL(gn_grad_apply_kernel, dim3(planes, ng_apply_blocks(hw)), dim3(256), 0, st, grad_y, x, residual, stats, gamma, beta, gain, w.coef, C, gc,
+        hipLaunchKernelGGL(gn_grad_apply_kernel, dim3(planes, aoc_plane_slices(hw)), dim3(256), 0, st, grad_y, x, residual, stats, gamma, beta, gain, w.coef, C, gc,
                            hw, relu, grad_x, grad_residual);
     AOC_RETURN_IF_LAUNCH_FAILED();
     return AOC_OK;

@@ -1,8 +1,8 @@
 // Training-time decoder tail: the backward of the shortcut stage of decoder_final (decoding_module.py:163, 170-176), the apply pass of a
 // "delta gate" (:126-130, :181-185: an IA_gate whose head carries the inter-object code of its own input's plane means), the prediction
 // head with the index of the background minimum (:144-160, 213-225) and their gradients.  Eight entry points (include/aoc_hip.h);
-// aoc_amd.tail_train wires them into autograd.  No existing kernel is touched: the forward of the head is repeated here term by term
-// (the pattern of cluster_grad.hip), so pred keeps aoc_logit_head's bits.
+// aoc_amd.tail_train wires them into autograd.  The bicubic weights are bicubic.h's, the forward's own; the head with its argmin is a
+// kernel of its own whose pred keeps aoc_logit_head's bits.
 //
 // No float atomics.  Every sum runs in an order fixed by the shapes and by the 16-byte alignment of the planes:
 //   bicubic adjoint  gather form.  u[I, j] = sum over the output columns J in ascending order, the taps k = 0..3 of each in turn, of
@@ -13,47 +13,16 @@
 //   plane sums       aoc_channel_scale_grad's order: thread t of T adds its front scalar, its float4 t, t + T, ... (.x .y .z .w in turn), its
 //                    back scalar, each product rounded first; the butterfly; the wave sums in ascending order.  T = 256 for planes of at most
 //                    2 048 float4, else 1 024.  The shortcut planes' dots ARE aoc_channel_scale_grad (called per object).
-// A streamed plane that is written is cut by the alignment of the written plane; the head's gradient cuts every plane by x's alignment
+// A streamed plane that is written is cut (plane_stream.h) by the alignment of the written plane; the head's gradient cuts every plane by x's alignment
 // (by grad_pred's for the bias column), whatever is written, so each output has the same bits alone as with the others.
-#include "aoc_common.h"
+#include "bicubic.h"
+#include "plane_stream.h"
 
 namespace {
 
-constexpr float BC_A = -0.75f;
 constexpr size_t TG_LDS_MAX = 64 * 1024;         // dynamic LDS a launch may ask for without an attribute
 
-typedef f32x4 f32x4_a4 __attribute__((aligned(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef i32x4 i32x4_a4 __attribute__((aligned(4)));
-__device__ __forceinline__ f32x4 tg_load4(const float *p) { return *reinterpret_cast<const f32x4_a4 *>(p); }
-__device__ __forceinline__ i32x4 tg_load4i(const int32_t *p) { return *reinterpret_cast<const i32x4_a4 *>(p); }
-__device__ __forceinline__ void tg_store4(float *p, const f32x4 v, bool aligned16) {
-    if (aligned16) __builtin_nontemporal_store(v, reinterpret_cast<f32x4 *>(p));
-    else *reinterpret_cast<f32x4_a4 *>(p) = v;
-}
-__device__ __forceinline__ int64_t tg_front(const void *p, int64_t hw) {
-    const int64_t n = ((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) / 4;
-    return n < hw ? n : hw;
-}
-
-// decoder_tail.hip's bicubic_taps, expression for expression: the forward and its adjoint share every weight's bits
-__device__ __forceinline__ f32x4 bicubic_taps(int o, int in, int out, int &i0) {
-    float t = 0.0f;
-    i0 = 0;
-    if (out > 1) {
-        const int64_t num = (int64_t)o * (in - 1);
-        i0 = (int)(num / (out - 1));
-        t = (float)(int)(num - (int64_t)i0 * (out - 1)) / (float)(out - 1);
-    }
-    const float x0 = t + 1.0f, u = 1.0f - t, x3 = u + 1.0f;
-    f32x4 wt;
-    wt.x = ((BC_A * x0 - 5.0f * BC_A) * x0 + 8.0f * BC_A) * x0 - 4.0f * BC_A;
-    wt.y = ((BC_A + 2.0f) * t - (BC_A + 3.0f)) * t * t + 1.0f;
-    wt.z = ((BC_A + 2.0f) * u - (BC_A + 3.0f)) * u * u + 1.0f;
-    wt.w = ((BC_A * x3 - 5.0f * BC_A) * x3 + 8.0f * BC_A) * x3 - 4.0f * BC_A;
-    return wt;
-}
-
+// a compare-and-select; decoder_tail.hip clamps with min(max()), which compiles to other instructions in these kernels, so each file keeps its own
 __host__ __device__ __forceinline__ int tg_clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 // the first output index whose second tap floor(o (in - 1) / (out - 1)) is >= s (out when there is none)
@@ -277,13 +246,13 @@ __global__ __launch_bounds__(256) void scale_shift_kernel(const float *__restric
     const float s = dpx ? dpx[k] / (float)hw : 0.0f;
     const float *sp = src + k * hw;
     float *op = out + plane * hw;
-    const int64_t front = tg_front(op, hw);
+    const int64_t front = aoc_front(op, hw);
     const int64_t body4 = (hw - front) / 4, back0 = front + body4 * 4;
     const int64_t tid = (int64_t)blockIdx.y * 256 + threadIdx.x, nthreads = (int64_t)gridDim.y * 256;
     if (tid < front) op[tid] = g * sp[tid] + s;
     for (int64_t i = tid; i < body4; i += nthreads) {
         const int64_t e = front + 4 * i;
-        const f32x4 v = tg_load4(sp + e);
+        const f32x4 v = aoc_load4(sp + e);
         f32x4 o;
 #pragma unroll
         for (int q = 0; q < 4; ++q) o[q] = g * v[q] + s;
@@ -292,14 +261,9 @@ __global__ __launch_bounds__(256) void scale_shift_kernel(const float *__restric
     if (tid < hw - back0) op[back0 + tid] = g * sp[back0 + tid] + s;
 }
 
-inline unsigned tg_slices(int64_t hw) {
-    const int64_t bx = (hw / 4 + 255) / 256;
-    return (unsigned)(bx < 1 ? 1 : (bx > 8 ? 8 : bx));
-}
-
 // ------------------------------------------------------------------------------------------ 3: the prediction head with its argmin
-// decoder_tail.hip's logit_head_kernel with an index beside every minimum: the channel sums are repeated term by term, so pred has
-// aoc_logit_head's bits.  The strict `<` keeps the lowest object of a tie within a wave (it walks its objects upwards); across the waves
+// decoder_tail.hip's logit_head_kernel with an index beside every minimum; the channel sums keep that kernel's order (sequential over c,
+// bias last), so pred has aoc_logit_head's bits (tested).  The strict `<` keeps the lowest object of a tie within a wave (it walks its objects upwards); across the waves
 // the lower index wins an equal value.  0 = no object (N == 1 writes nothing; every bg logit NaN or +inf selects none).
 constexpr int LH_MAXW = 4;
 __global__ __launch_bounds__(64 * LH_MAXW) void logit_head_argmin_kernel(const float *__restrict__ x, const float *__restrict__ wb_fg,
@@ -390,7 +354,7 @@ __global__ __launch_bounds__(T) void logit_head_grad_kernel(const float *__restr
     const float *xp = bias ? nullptr : x + ((size_t)n * C + c) * hw;
     float *op = (grad_x && !bias) ? grad_x + ((size_t)n * C + c) * hw : nullptr;
     const float wf = op ? wb_fg[(size_t)n * stride + c] : 0.0f, wg = (op && sel) ? wb_bg[(size_t)n * stride + c] : 0.0f;
-    const int64_t front = tg_front(bias ? (const void *)gn : (const void *)xp, hw);
+    const int64_t front = aoc_front(bias ? (const void *)gn : (const void *)xp, hw);
     const int64_t body4 = (hw - front) / 4, back0 = front + body4 * 4;
     const bool op16 = op && ((reinterpret_cast<uintptr_t>(op + front) & 15) == 0);
     float af = 0.0f, ab = 0.0f;
@@ -408,25 +372,25 @@ __global__ __launch_bounds__(T) void logit_head_grad_kernel(const float *__restr
     if (t < front) one(t);
     for (int64_t i = t; i < body4; i += T) {
         const int64_t e = front + 4 * i;
-        const f32x4 a4 = tg_load4(gn + e);
+        const f32x4 a4 = aoc_load4(gn + e);
         f32x4 b4 = {0.0f, 0.0f, 0.0f, 0.0f}, x4 = {1.0f, 1.0f, 1.0f, 1.0f}, o4;
         bool hit[4] = {false, false, false, false};
         if (sel) {
-            const i32x4 r4 = tg_load4i(arg + e);
-            const f32x4 g04 = tg_load4(g + e);
+            const i32x4 r4 = aoc_load4i(arg + e);
+            const f32x4 g04 = aoc_load4(g + e);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 hit[q] = r4[q] == n;
                 b4[q] = hit[q] ? g04[q] : 0.0f;
             }
         }
-        if (!bias && sums) x4 = tg_load4(xp + e);
+        if (!bias && sums) x4 = aoc_load4(xp + e);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             if (sums) { af += a4[q] * x4[q]; ab += hit[q] ? b4[q] * x4[q] : 0.0f; }
             o4[q] = hit[q] ? a4[q] * wf + b4[q] * wg : a4[q] * wf;
         }
-        if (op) tg_store4(op + e, o4, op16);
+        if (op) aoc_store4(op + e, o4, op16);
     }
     if (t < hw - back0) one(back0 + t);
     if (!sums) return;
@@ -538,7 +502,7 @@ int aoc_shortcut_stage_grad_apply(const float *grad_out, const float *gain, cons
     }
     if (grad_low) {
         const int64_t HW = (int64_t)H * W;
-        hipLaunchKernelGGL(scale_shift_kernel, dim3((unsigned)((int64_t)N * Cr), tg_slices(HW)), dim3(256), 0, st, grad_out, gain, dpx, Cr, Ctot, Ce, HW,
+        hipLaunchKernelGGL(scale_shift_kernel, dim3((unsigned)((int64_t)N * Cr), aoc_plane_slices(HW)), dim3(256), 0, st, grad_out, gain, dpx, Cr, Ctot, Ce, HW,
                            grad_low);
         AOC_RETURN_IF_LAUNCH_FAILED();
     }
@@ -548,7 +512,7 @@ int aoc_shortcut_stage_grad_apply(const float *grad_out, const float *gain, cons
 int aoc_delta_gate_grad_apply(const float *grad_y, const float *gain, const float *dpx, int N, int C, int64_t hw, float *grad_x, aoc_stream_t stream) {
     if (!grad_y || !gain || !grad_x || N < 1 || C < 1 || hw < 1) return AOC_ERR_INVALID_ARG;
     if (N > AOC_MAX_OBJECTS || (int64_t)N * C > 0x7fffffffLL) return AOC_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(scale_shift_kernel, dim3((unsigned)((int64_t)N * C), tg_slices(hw)), dim3(256), 0, aoc_hip_stream(stream), grad_y, gain, dpx, C, C, 0, hw,
+    hipLaunchKernelGGL(scale_shift_kernel, dim3((unsigned)((int64_t)N * C), aoc_plane_slices(hw)), dim3(256), 0, aoc_hip_stream(stream), grad_y, gain, dpx, C, C, 0, hw,
                        grad_x);
     AOC_RETURN_IF_LAUNCH_FAILED();
     return AOC_OK;
