@@ -1470,6 +1470,75 @@ int aoc_prehead_grad(const float *grad_out, const float *feat, const float *stat
                      float *grad_bias, float *grad_gamma, float *grad_beta, float *grad_emb_hwc, void *workspace, size_t workspace_bytes,
                      aoc_stream_t stream);
 
+/*
+ * The training update (csrc/optim.hip; aoc_amd.optim_train): the lines of the reference trainer between loss.backward() and the next forward,
+ *   train_manager_mm.py:283       torch.nn.utils.clip_grad_norm_(model.parameters(), cfg.TRAIN_CLIP_GRAD_NORM)
+ *   train_manager_mm.py:68-72     optim.SGD(trainable_params, lr, momentum=0.9, nesterov=True)     (one group per parameter: utils/learning.py:24-34)
+ *   train_manager_mm.py:284       optimizer.step()
+ * over a TABLE of tensors, so that a step is three launches for the whole model and five parameter-sized streams (read g, p and the momentum
+ * buffer, write p and the buffer) plus one read of g for the norm, where torch's single-tensor path (torch/optim/sgd.py: _single_tensor_sgd,
+ * the only one open with a group per parameter) runs several launches per tensor and about fifteen streams.
+ *
+ * The table is a DEVICE array of n_tensors records; `table_host` is the host array it was uploaded from (pinned or not).  The library copies
+ * nothing: table_host is read by the host code to validate the call BEFORE anything is enqueued or written -- n >= 0, chunk_begin the running
+ * prefix, their total == n_chunks <= 2^31 - 1, and for the step a non-NULL param (and momentum, when momentum != 0) wherever grad is set;
+ * AOC_ERR_INVALID_ARG otherwise.  It may be NULL (a table built on the device): then only the scalars are checked and the records are trusted.
+ * A tensor is cut into chunks of AOC_MT_CHUNK floats counted from its FIRST ELEMENT; chunk_begin is the number of chunks of the tensors in
+ * front (an empty tensor owns none); one workgroup of 256 threads takes one chunk and finds its tensor by a binary search over chunk_begin
+ * (no host-built chunk map).  A record whose grad is NULL is skipped everywhere: its parameter and buffer are not touched, and it adds nothing
+ * to the norm.  All pointers are class 4: every access goes through 4-byte-aligned vector types, a tensor may start at any float, and no
+ * summation order depends on an address -- the norm's bits do not depend on any pointer's alignment.  fp32, no float atomics: equal buffers
+ * give equal bits.
+ */
+#define AOC_MT_CHUNK 4096           /* floats per chunk: 16 per thread and stream, as four 16-byte accesses 4 KiB apart */
+#define AOC_MT_HAS_MOMENTUM 1       /* aoc_mt_tensor.flags bit 0: the momentum buffer holds a value                   */
+typedef struct aoc_mt_tensor {
+    float *param;                    /* [n]; may be NULL for the norm, the scale and the zeroing */
+    float *grad;                     /* [n] or NULL: the tensor has no gradient this step        */
+    float *momentum;                 /* [n]; may be NULL when momentum == 0                      */
+    int64_t n;
+    int64_t chunk_begin;
+    float weight_decay;
+    int32_t flags;
+} aoc_mt_tensor;
+int64_t aoc_mt_chunks(int64_t n);   /* ceil(n / AOC_MT_CHUNK); 0 for n <= 0 */
+/* aoc_grad_sumsq_partials: partial[c] (n_chunks doubles, 8-byte aligned) = the sum of g^2 over chunk c: thread t of 256 owns the floats
+ * 1024 j + 4 t .. + 3 of the chunk (j = 0 .. 3) and adds their squares in ascending address in float32 from 0.0f, each square rounded before it
+ * is added; then the xor butterfly over the wave (32 .. 1), then the four wave sums ascending ((w0 + w1) + w2) + w3; widened to double.  Floats
+ * behind the tensor's end count as +0.0f; a chunk of a tensor without grad gives 0.0.  The first half of clip_grad_norm_ (norm_type 2). */
+int aoc_grad_sumsq_partials(const aoc_mt_tensor *table, const aoc_mt_tensor *table_host, int n_tensors, int64_t n_chunks, double *partial,
+                            aoc_stream_t stream);
+/* aoc_grad_norm_finish: one workgroup; thread t adds partial[t], partial[t + 256], ... ascending in double from 0.0, the xor butterfly
+ * (32 .. 1) and the four wave sums ascending, all in double; total_norm[0] = (float)sqrt(sum); coef[0] = c > 1 ? 1 : c with
+ * c = max_norm / (total_norm + 1e-6f) in float32 (torch/nn/utils/clip_grad.py: clip_coef and its clamp(max=1.0); a NaN stays a NaN).  Both are
+ * device words, each optional (not both NULL); nothing synchronises.  n_chunks == 0 gives total_norm 0. */
+int aoc_grad_norm_finish(const double *partial, int64_t n_chunks, float max_norm, float *total_norm, float *coef, aoc_stream_t stream);
+/* aoc_multi_tensor_scale: g = g * coef[0] in place for every record with a grad: the second half of a stand-alone clip_grad_norm_
+ * (train_manager_mm.py:283).  aoc_multi_tensor_zero: g = 0.0f likewise (optimizer.zero_grad(set_to_none=False) as one launch). */
+int aoc_multi_tensor_scale(const aoc_mt_tensor *table, const aoc_mt_tensor *table_host, int n_tensors, int64_t n_chunks, const float *coef,
+                           aoc_stream_t stream);
+int aoc_multi_tensor_zero(const aoc_mt_tensor *table, const aoc_mt_tensor *table_host, int n_tensors, int64_t n_chunks, aoc_stream_t stream);
+/* aoc_sgd_step: train_manager_mm.py:284 with the clip of :283 folded in.  Per element, in this order, each operation rounded once (nothing fuses):
+ *   g' = g * coef[0]                                                     (coef == NULL: 1.0f)
+ *   d  = (wd != 0) ? g' + wd * p : g'                                    wd = the record's weight_decay; the clip first, the decay second
+ *   b' = (flags & 1) ? momentum * b + (1.0f - dampening) * d : d         (skipped when momentum == 0; 1.0f - dampening formed once in float32)
+ *   v  = nesterov ? d + momentum * b' : b'                               (v = d when momentum == 0)
+ *   p' = p + (-lr) * v                                                   lr = lr_dev[tensor] when lr_dev != NULL (n_tensors device floats), else `lr`
+ * which is torch's _single_tensor_sgd behind clip_grad_norm_.  Writes p' and b'; g is read with the non-temporal load and is written only with
+ * zero_grad != 0, as 0.0f (the clipped value is never written back).  After a step with momentum != 0 bit 0 of `flags` is set in every record
+ * that had a grad and n > 0 -- in the device table by one small launch behind the step, and in table_host by the host code, so that the mirror
+ * keeps describing the device table and nothing is uploaded again; once every such record carries the bit that launch is not made.
+ * AOC_ERR_INVALID_ARG: momentum < 0 (or NaN), nesterov with momentum == 0 or dampening != 0 (torch's own rule), and the table checks above. */
+int aoc_sgd_step(aoc_mt_tensor *table, aoc_mt_tensor *table_host, int n_tensors, int64_t n_chunks, const float *coef, float lr, const float *lr_dev,
+                 float momentum, float dampening, int nesterov, int zero_grad, aoc_stream_t stream);
+/* aoc_clip_sgd_step: aoc_grad_sumsq_partials, aoc_grad_norm_finish and aoc_sgd_step as ONE call: exactly those launches, with the partial
+ * sums and the coefficient in the caller's workspace (8-byte aligned; aoc_clip_sgd_step_workspace_bytes(n_chunks), else AOC_ERR_WORKSPACE), so
+ * every output has the bits of the separate calls.  total_norm (a device word) is required.  Everything is validated before the first launch. */
+size_t aoc_clip_sgd_step_workspace_bytes(int64_t n_chunks);
+int aoc_clip_sgd_step(aoc_mt_tensor *table, aoc_mt_tensor *table_host, int n_tensors, int64_t n_chunks, float max_norm, float *total_norm, float lr,
+                      const float *lr_dev, float momentum, float dampening, int nesterov, int zero_grad, void *workspace, size_t workspace_bytes,
+                      aoc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

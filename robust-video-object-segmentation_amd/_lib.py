@@ -177,6 +177,14 @@ SIGNATURES = {
     "aoc_upsample_ce_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "aoc_prehead_grad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i64]),
     "aoc_prehead_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "aoc_mt_chunks": (_i64, [_i64]),
+    "aoc_grad_sumsq_partials": (_i, [_vp, _vp, _i, _i64, _vp, _vp]),
+    "aoc_grad_norm_finish": (_i, [_vp, _i64, _f, _vp, _vp, _vp]),
+    "aoc_multi_tensor_scale": (_i, [_vp, _vp, _i, _i64, _vp, _vp]),
+    "aoc_multi_tensor_zero": (_i, [_vp, _vp, _i, _i64, _vp]),
+    "aoc_sgd_step": (_i, [_vp, _vp, _i, _i64, _vp, _f, _vp, _f, _f, _i, _i, _vp]),
+    "aoc_clip_sgd_step_workspace_bytes": (_sz, [_i64]),
+    "aoc_clip_sgd_step": (_i, [_vp, _vp, _i, _i64, _f, _vp, _f, _vp, _f, _f, _i, _i, _vp, _sz, _vp]),
 }
 
 STATUS = {0: "AOC_OK", -1: "AOC_ERR_INVALID_ARG", -2: "AOC_ERR_WORKSPACE", -3: "AOC_ERR_LAUNCH", -4: "AOC_ERR_UNSUPPORTED"}
