@@ -20,15 +20,16 @@ so the entry is the backward of a plain product); ``bn1`` goes through ``decoder
 Without a wanted gradient the forward returns the mirror's result through the mirror's own calls; with one it calls the same C entry points,
 so the output bits are the mirror's at the same ``fused`` flag.  Frozen parameters and ``ctx.needs_input_grad`` select which optional outputs
 the kernels are asked for.  All backwards are ``once_differentiable``; every sum runs in a fixed order without float atomics.  The ctypes
-wrappers of the new entry points live here, not in ``ops`` (whose public names are a tested table); they keep ``ops``' tensor contract: inputs
-converted by ``_f32c`` into names that live until the call, caller outputs checked by ``_out``, addresses only through ``_p`` / ``_addr``.
+wrappers of the new entry points live here, not in ``ops`` (whose public names are a tested table); they keep ``ops``' tensor contract through its
+helpers: inputs converted by ``_f32c`` / ``_opt`` into names that live until the call, caller outputs checked by ``_out`` (the named optional
+ones chosen by ``_wanted``), addresses only through ``_p`` / ``_addr``.
 """
 import torch
 from torch import nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib, aspp, decoder_train, gates_train, ops
-from .matching_train import _wants_grad
+from .ops import _det, _new, _opt, _planes_hw, _wanted, _wants_grad
 
 
 # ------------------------------------------------------------------------------------------ the C ABI
@@ -40,17 +41,6 @@ def _same_shape_list(what, ts, like=None):
     if any(tuple(t.shape) != shape for t in ts):
         raise ValueError(f"{what}: the listed tensors {[tuple(t.shape) for t in ts]} do not all have shape {shape}")
     return ts
-
-
-def _planes_hw(what, x):
-    if x.dim() < 2 or x.numel() == 0:
-        raise ValueError(f"{what}: expected a non-empty [N, C, ...] tensor, got {tuple(x.shape)}")
-    planes = x.shape[0] * x.shape[1]
-    return planes, x.numel() // planes
-
-
-def _new(like, *shape):
-    return torch.empty(*shape, dtype=torch.float32, device=like.device)
 
 
 def plane_dot_multi(x, gs, dots=None):
@@ -84,18 +74,13 @@ def gct_gate_multi_backward(dgate, gate, plane_sums, alpha, gamma, beta, eps, l1
     if not (al.shape[0] == ga.shape[0] == be.shape[0] == n_set):
         raise ValueError(f"gct_gate_multi_backward: {n_set} sets, parameters for {al.shape[0]}, {ga.shape[0]}, {be.shape[0]}")
     out = dict(out or {})
-    if set(out) - set(_GATE_OUTS):
-        raise ValueError(f"gct_gate_multi_backward: unknown outputs {sorted(set(out) - set(_GATE_OUTS))}")
     ops._need_gpu(dgate, gate, plane_sums, al, ga, be, *out.values())
-    shapes = ((N, C), (n_set, N, C), (n_set, C), (n_set, C), (n_set, C))
-    bufs = []
-    for name, shape, w in zip(_GATE_OUTS, shapes, want):
-        bufs.append(ops._out("gct_gate_multi_backward: " + name, out[name], shape) if name in out else (_new(dgate, *shape) if w else None))
+    bufs = _wanted("gct_gate_multi_backward", _GATE_OUTS, ((N, C), (n_set, N, C), (n_set, C), (n_set, C), (n_set, C)), want, out, dgate)
     L = _lib.lib()
     ws = ops._ws(L.aoc_gct_gate_multi_grad_workspace_bytes(n_set, N, C), dgate.device)
     _lib.check(L.aoc_gct_gate_multi_grad(ops._p(dgate), ops._p(gate), ops._p(plane_sums), ops._p(al), ops._p(ga), ops._p(be), n_set, N, C, float(eps),
                                          int(bool(l1_mode)), *(ops._p(b) for b in bufs), ops._p(ws), ws.numel(), ops._stream()), "aoc_gct_gate_multi_grad")
-    return tuple(bufs)
+    return bufs
 
 
 def channel_scale_multi_backward_apply(gs, gates, x, dsum_total, dmean=None, grad_x=None):
@@ -105,7 +90,7 @@ def channel_scale_multi_backward_apply(gs, gates, x, dsum_total, dmean=None, gra
     planes, hw = _planes_hw("channel_scale_multi_backward_apply", x)
     gs = _same_shape_list("channel_scale_multi_backward_apply", gs, x)
     gates, dsum_total = ops._f32c(gates), ops._f32c(dsum_total)
-    dmean = ops._f32c(dmean) if dmean is not None else None
+    dmean = _opt(dmean)
     if gates.numel() != len(gs) * planes or dsum_total.numel() != planes or (dmean is not None and dmean.numel() != planes):
         raise ValueError(f"channel_scale_multi_backward_apply: gates {tuple(gates.shape)}, dsum_total {tuple(dsum_total.shape)} or dmean do not fit "
                          f"{len(gs)} sets of x {tuple(x.shape)}")
@@ -190,23 +175,17 @@ def groupnorm_cat_relu_backward(grad_out, us, stats, groups, gamma, beta, tail, 
     else:
         grad_u = [torch.empty_like(us[0]) if w else None for w in want_u]
     shapes = ((n_src, C), (n_src, C), (N, C_tail), (C_total,), (C_total,), (C_total,))
-    small = []
-    for name, shape, w in zip(_CAT_OUTS[1:], shapes, want[1:]):
-        small.append(ops._out(f"{what}: {name}", out[name], shape) if name in out else (_new(grad_out, *shape) if (w and shape[-1] > 0) else None))
+    small = _wanted(what, _CAT_OUTS[1:], shapes, want[1:], {k: v for k, v in out.items() if k != "grad_u"}, grad_out)
     ops._need_gpu(grad_out, stats, plane_sumsq, gate, al, ga, g, b, tail, *us, *grad_u, *small)
     L = _lib.lib()
     ws = ops._ws(L.aoc_groupnorm_cat_relu_grad_workspace_bytes(n_src, N, C, C_tail, groups), grad_out.device)
     _lib.check(L.aoc_groupnorm_cat_relu_grad(ops._p(grad_out), ops._ptr_array(us), n_src, N, C, hw, groups, ops._p(stats), ops._p(g), ops._p(b), ops._p(tail),
                                              C_tail, ops._p(plane_sumsq), ops._p(gate), ops._p(al), ops._p(ga), float(gct_eps), ops._ptr_array(grad_u),
                                              *(ops._p(t) for t in small), ops._p(ws), ws.numel(), ops._stream()), "aoc_groupnorm_cat_relu_grad")
-    return (grad_u,) + tuple(small)
+    return (grad_u,) + small
 
 
 # ------------------------------------------------------------------------------------------ the fused stages
-def _det(t):
-    return ops._f32c(t.detach()) if t is not None else None
-
-
 class _GateInputs(torch.autograd.Function):
     """x [N, C, ...], then n_set alphas, n_set gammas, n_set betas ([1, C, 1, 1]) -> (GCT_0(x), ..., GCT_{n_set-1}(x), plane means [N, C]) by
     aoc_plane_sum_sumsq, aoc_gct_gate_multi, aoc_channel_scale_multi (``aspp.gate_inputs``' calls); saves x, the plane sums of squares, the gates."""

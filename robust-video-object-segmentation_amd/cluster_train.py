@@ -23,9 +23,10 @@ import torch
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
-from . import _lib, matching, ops
+from . import matching, ops
 from .matching import DEFAULT_CLUSTER_NUM
-from .matching_train import _bias_arg, _wants_grad
+from .matching_train import _bias_arg, _guard
+from .ops import _wants_grad
 
 
 def _plane_sets(levels, n_obj, kmax, m):
@@ -95,11 +96,8 @@ def global_matching_cluster2(reference_embeddings, query_embeddings, reference_l
         out = matching.global_matching_for_eval_cluster([reference_embeddings], query_embeddings, [labels], n_chunks, dis_bias, ori_size, 1,
                                                         use_float16, 0, init_rows, cluster_num)
         return torch.ones(1, h, w, reference_labels.size(2), 2, device=query_embeddings.device) if out.shape[-1] == 1 else out
-    if use_float16:
-        raise _lib.AocHipError("aoc_amd.cluster_train.global_matching_cluster2: use_float16=True has no backward (scipy's kmeans2 rejects float16 and "
-                               "the reference degrades to a constant, AEM:275-286); pass use_float16=False, as the model does with "
-                               "MODEL_FLOAT16_MATCHING = False")
-    ops._need_gpu(*[t for t in (reference_embeddings, query_embeddings, reference_labels, dis_bias) if torch.is_tensor(t)])
+    _guard("global_matching_cluster2", use_float16, reference_embeddings, query_embeddings, reference_labels, dis_bias, module="cluster_train",
+           why="scipy's kmeans2 rejects float16 and the reference degrades to a constant, AEM:275-286")
     assert reference_embeddings.size()[:2] == reference_labels.size()[:2]         # AEM:430
     h, w, embedding_dim = query_embeddings.size()
     obj_nums = reference_labels.size(2)

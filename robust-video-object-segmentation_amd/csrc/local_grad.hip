@@ -18,17 +18,12 @@
 //
 // Kernel shapes are first choices (one workgroup per previous-frame pixel, one wave per query pixel, consecutive channels that share a
 // winner are NOT merged): nothing here has been tuned on a profile yet.
-#include "aoc_common.h"
+#include "local_window.h"
 
 namespace {
 
-constexpr int LG_MAX_RADII = 8;
 constexpr int LG_MAX_WINDOW = 31;
 constexpr int LG_BIAS_PIX = 256;    // pixels per first-stage block of the bias sum
-struct LgRadii {
-    int32_t r[LG_MAX_RADII];
-    int32_t n;
-};
 
 // Monotone uint32 image of a float: a < b  <=>  image(a) < image(b) (distances can round slightly below zero, so the plain bit pattern
 // would not do).  Negative floats have all bits flipped, the others the sign bit set.
@@ -64,7 +59,7 @@ __device__ __forceinline__ void lg_emit(const unsigned long long *keys, int nr, 
 // array per workgroup (LDS atomics are workgroup-wide): 16 queries x n_radii x n_obj x 8 B, 30 KB at most.
 template <int TMAX>
 __global__ __launch_bounds__(256) void lg_window_reg_argmin_kernel(const float *__restrict__ query, const float *__restrict__ prev,
-                                                                    const uint32_t *__restrict__ right_bits, int H, int W, LgRadii radii,
+                                                                    const uint32_t *__restrict__ right_bits, int H, int W, LocalRadii radii,
                                                                     const float *__restrict__ obj_bias, int n_obj, float *__restrict__ out,
                                                                     int32_t *__restrict__ arg, int transform, int rate) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -86,7 +81,7 @@ __global__ __launch_bounds__(256) void lg_window_reg_argmin_kernel(const float *
     const int y0 = blockIdx.y * 2;
 
     for (int i = threadIdx.x; i < n_keys; i += blockDim.x) lkey[i] = lg_pad_key();           // AEM:1032 pad
-    if ((int)threadIdx.x <= RA) {
+    if ((int)threadIdx.x <= RA) {            // lw_ring_classes, written out as in local_window_reg_kernel: this kernel stays that one's copy, line by line
         int c = 0;
         while (radii.r[c] < (int)threadIdx.x) ++c;
         lcls[threadIdx.x] = c;
@@ -206,22 +201,18 @@ __global__ __launch_bounds__(256) void lg_window_reg_argmin_kernel(const float *
 // Every other width (C % 4 == 0, C <= 128): one workgroup per query pixel, a thread per window position.  Norms and the dot product are
 // plain sequential sums (held to the float64 bound, not to aoc_local_window_match_ex's bits).
 __global__ __launch_bounds__(256) void lg_window_argmin_kernel(const float *__restrict__ query, const float *__restrict__ prev,
-                                                                const uint32_t *__restrict__ right_bits, int H, int W, int C, LgRadii radii,
+                                                                const uint32_t *__restrict__ right_bits, int H, int W, int C, LocalRadii radii,
                                                                 const float *__restrict__ obj_bias, int n_obj, float *__restrict__ out,
                                                                 int32_t *__restrict__ arg, int transform, int rate) {
     __shared__ __attribute__((aligned(16))) float lq[128];
     __shared__ int32_t lcls[LG_MAX_WINDOW + 1];
-    __shared__ unsigned long long lkey[LG_MAX_RADII * AOC_MAX_OBJECTS];
+    __shared__ unsigned long long lkey[LW_MAX_RADII * AOC_MAX_OBJECTS];
     const int nr = radii.n;
     const int RA = radii.r[nr - 1];
     const int y = blockIdx.y, x = blockIdx.x;
     const int tid = threadIdx.x;
     for (int i = tid; i < nr * n_obj; i += blockDim.x) lkey[i] = lg_pad_key();               // AEM:1032 pad
-    if (tid <= RA) {
-        int c = 0;
-        while (radii.r[c] < tid) ++c;
-        lcls[tid] = c;
-    }
+    lw_ring_classes(radii, RA, lcls);
     for (int c = tid; c < C; c += blockDim.x) lq[c] = query[((size_t)y * W + x) * C + c];
     __syncthreads();
     float q2 = 0.0f;
@@ -282,8 +273,8 @@ __global__ __launch_bounds__(256) void lg_gate_kernel(const float *__restrict__ 
 // One wave per query pixel: acc += (2 g) * (q - p_arg) over (o, ch), ascending.
 __global__ __launch_bounds__(64) void lg_query_kernel(const float *__restrict__ gbuf, const int32_t *__restrict__ abuf, const float *__restrict__ query,
                                                       const float *__restrict__ prev, int C, int P, float *__restrict__ grad_query) {
-    __shared__ float lg2[LG_MAX_RADII * AOC_MAX_OBJECTS];
-    __shared__ int32_t la[LG_MAX_RADII * AOC_MAX_OBJECTS];
+    __shared__ float lg2[LW_MAX_RADII * AOC_MAX_OBJECTS];
+    __shared__ int32_t la[LW_MAX_RADII * AOC_MAX_OBJECTS];
     const int64_t i = blockIdx.x;
     const int lane = threadIdx.x;
     for (int p = lane; p < P; p += 64) {
@@ -392,8 +383,8 @@ LgLayout lg_layout(int H, int W, int n_radii, int n_obj) {
 // 0 = fine
 int lg_check_sizes(int H, int W, int C, int n_radii, int n_obj) {
     if (H < 1 || W < 1 || C < 1 || n_radii < 1 || n_obj < 1) return AOC_ERR_INVALID_ARG;
-    if (C > AOC_MAX_CHANNELS || n_radii > LG_MAX_RADII || n_obj > AOC_MAX_OBJECTS) return AOC_ERR_UNSUPPORTED;
-    if ((int64_t)H * W >= (1ll << 31) / (LG_MAX_RADII * AOC_MAX_OBJECTS)) return AOC_ERR_UNSUPPORTED;     // int32 pixel and entry indices
+    if (C > AOC_MAX_CHANNELS || n_radii > LW_MAX_RADII || n_obj > AOC_MAX_OBJECTS) return AOC_ERR_UNSUPPORTED;
+    if ((int64_t)H * W >= (1ll << 31) / (LW_MAX_RADII * AOC_MAX_OBJECTS)) return AOC_ERR_UNSUPPORTED;     // int32 pixel and entry indices
     return AOC_OK;
 }
 
@@ -407,16 +398,10 @@ int aoc_local_window_match_argmin(const float *query, const float *prev, const u
     if (!query || !prev || !right_bits || !radii_host || !out || !arg) return AOC_ERR_INVALID_ARG;
     if (aoc_off16(query, prev)) return AOC_ERR_INVALID_ARG;                // float4 pixel rows in both kernels
     if (H < 1 || W < 1 || C < 4 || n_radii < 1 || n_obj < 1 || atrous_rate < 1) return AOC_ERR_INVALID_ARG;
-    if ((C & 3) || C > 128 || n_radii > LG_MAX_RADII || n_obj > AOC_MAX_OBJECTS) return AOC_ERR_UNSUPPORTED;
+    if ((C & 3) || C > 128 || n_radii > LW_MAX_RADII || n_obj > AOC_MAX_OBJECTS) return AOC_ERR_UNSUPPORTED;
     if ((int64_t)H * W >= (1ll << 31) - 1) return AOC_ERR_UNSUPPORTED;                 // the pixel index is a key's low word, -1 is "none"
-    LgRadii radii;
-    radii.n = n_radii;
-    // window radii in units of the atrous rate: AEM:949 pad_max_distance = max - max % rate, AEM:1039 local_dis // rate
-    for (int i = 0; i < n_radii; ++i) {
-        if (radii_host[i] < 0 || (i > 0 && radii_host[i] <= radii_host[i - 1])) return AOC_ERR_INVALID_ARG;
-        radii.r[i] = radii_host[i] / atrous_rate;
-    }
-    for (int i = n_radii; i < LG_MAX_RADII; ++i) radii.r[i] = radii.r[n_radii - 1];
+    LocalRadii radii;
+    if (int rc = lw_radii_from_host(radii_host, n_radii, atrous_rate, radii)) return rc;
     if (radii.r[n_radii - 1] * atrous_rate > LG_MAX_WINDOW) return AOC_ERR_UNSUPPORTED;
     hipStream_t st = aoc_hip_stream(stream);
     if (C == 100 || C == 128) {

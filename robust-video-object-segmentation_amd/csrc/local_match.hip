@@ -9,7 +9,7 @@
 // the nested-window minima of AEM:1036-1046 are a prefix-min over rings at the end.
 #include <algorithm>
 
-#include "aoc_common.h"
+#include "local_window.h"
 
 namespace {
 
@@ -19,14 +19,7 @@ __device__ __forceinline__ void lds_fmin(float *p, float v) {
 #endif
 }
 
-constexpr int LM_MAX_RADII = 8;
-struct LocalRadii {
-    int32_t r[LM_MAX_RADII];
-    int32_t n;
-};
-
-// radii are in units of the atrous rate (ring a = max(|dy|, |dx|) / rate; only offsets that are multiples of the rate exist,
-// AEM:949-959 unfold with stride = atrous_rate); R = rate * radii.r[n-1] is the window half-size in pixels.
+// radii are in units of the atrous rate (lw_radii_from_host, local_window.h); R = rate * radii.r[n-1] is the window half-size in pixels.
 // f16 != 0: the reference's `.half()` mode (AEM:1002-1005): operands, norms, dot products and distances rounded to float16.
 template <int TMAX>
 __global__ __launch_bounds__(256) void local_window_kernel(const float *__restrict__ query, const float *__restrict__ prev,
@@ -54,11 +47,7 @@ __global__ __launch_bounds__(256) void local_window_kernel(const float *__restri
     const int y = y0 + wave;
 
     for (int i = threadIdx.x; i < 4 * acc_per_wave; i += blockDim.x) lacc[i] = padv;   // AEM:1032 pad
-    if ((int)threadIdx.x <= RA) {
-        int c = 0;
-        while (radii.r[c] < (int)threadIdx.x) ++c;
-        lcls[threadIdx.x] = c;
-    }
+    lw_ring_classes(radii, RA, lcls);
 
     float a[TMAX], q2 = 0.0f, q2r[4];
     {   // A fragment: 16 query pixels of row y (clamped when y >= H; such waves never accumulate)
@@ -219,7 +208,7 @@ __global__ __launch_bounds__(256) void local_window_reg_kernel(const float *__re
     const int y0 = blockIdx.y * 2;
 
     for (int i = lane; i < acc_per_wave; i += 64) my_acc[i] = padv;      // AEM:1032 pad
-    if ((int)threadIdx.x <= RA) {
+    if ((int)threadIdx.x <= RA) {            // lw_ring_classes, written out: with the routine both instantiations come out two instructions longer
         int c = 0;
         while (radii.r[c] < (int)threadIdx.x) ++c;
         lcls[threadIdx.x] = c;
@@ -563,15 +552,9 @@ static int local_window_match_impl(const float *query, const float *prev, const 
     if (!query || !prev || !right_bits || !radii_host || !out) return AOC_ERR_INVALID_ARG;
     if (aoc_off16(query, prev, prev2)) return AOC_ERR_INVALID_ARG;         // float4 pixel rows (both kernels read prev so, the register kernel query too)
     if (H < 1 || W < 1 || C < 4 || n_radii < 1 || n_obj < 1 || atrous_rate < 1) return AOC_ERR_INVALID_ARG;
-    if ((C & 3) || C > 128 || n_radii > LM_MAX_RADII || n_obj > AOC_MAX_OBJECTS) return AOC_ERR_UNSUPPORTED;
+    if ((C & 3) || C > 128 || n_radii > LW_MAX_RADII || n_obj > AOC_MAX_OBJECTS) return AOC_ERR_UNSUPPORTED;
     LocalRadii radii;
-    radii.n = n_radii;
-    // window radii in units of the atrous rate: AEM:949 pad_max_distance = max - max % rate, AEM:1039 local_dis // rate
-    for (int i = 0; i < n_radii; ++i) {
-        if (radii_host[i] < 0 || (i > 0 && radii_host[i] <= radii_host[i - 1])) return AOC_ERR_INVALID_ARG;
-        radii.r[i] = radii_host[i] / atrous_rate;
-    }
-    for (int i = n_radii; i < LM_MAX_RADII; ++i) radii.r[i] = radii.r[n_radii - 1];
+    if (int rc = lw_radii_from_host(radii_host, n_radii, atrous_rate, radii)) return rc;
     const int rate = atrous_rate, f16 = float16 ? 1 : 0;
     const int R = radii.r[n_radii - 1] * atrous_rate;
     if (R > 31) return AOC_ERR_UNSUPPORTED;

@@ -21,8 +21,8 @@ calls the same C entry points, so the output bits are the mirror's.  The gain th
 forward kernel's own dot product (summation order only; the tests' bounds cover it), as in ``gates_train``.  Frozen parameters and
 ``ctx.needs_input_grad`` select which optional outputs the kernels are asked for.  All backwards are ``once_differentiable``; every sum runs
 in a fixed order without float atomics.  The ctypes wrappers of the two new entry points live here, not in ``ops`` (whose public names are a
-tested table); they keep ``ops``' tensor contract: inputs converted by ``_f32c`` into names that live until the call, caller outputs checked
-by ``_out``, addresses only through ``_p``.
+tested table); they keep ``ops``' tensor contract through its helpers: inputs converted by ``_f32c`` / ``_opt`` / ``_vec`` into names that live
+until the call, caller outputs checked by ``_out`` (the named optional ones chosen by ``_wanted``), addresses only through ``_p``.
 """
 import torch
 from torch import nn
@@ -30,28 +30,22 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib, gates_train, ops
 from .decoder_memory import select_memory
-from .matching_train import _wants_grad
+from .ops import _det, _opt, _planes_hw, _vec, _wanted, _wants_grad
 
 
 # ------------------------------------------------------------------------------------------ the C ABI
 def _gn_shape(what, x, groups):
-    if x.dim() < 2 or x.numel() == 0:
-        raise ValueError(f"{what}: expected a non-empty [N, C, ...] tensor, got {tuple(x.shape)}")
+    _, hw = _planes_hw(what, x)
     N, C = x.shape[0], x.shape[1]
     if int(groups) < 1 or C % int(groups):
         raise ValueError(f"{what}: {C} channels do not divide into {groups} groups")
-    return N, C, x.numel() // (N * C)
-
-
-def _vec(t):
-    return ops._f32c(t).reshape(-1) if t is not None else None
+    return N, C, hw
 
 
 def groupnorm_relu_forward(x, groups, gamma, beta, eps=1e-5, residual=None, relu=True, gate=None):
     """ops.groupnorm_relu, or with ``gate`` = (head, weight, bias) ops.groupnorm_relu_scale, keeping the statistics: -> (y, stats
     [N * groups, 2] = (mean, rstd), a view of the call's workspace).  The same C entries as the mirror's wrappers, so y has their bits."""
-    x = ops._f32c(x)
-    residual = ops._f32c(residual) if residual is not None else None
+    x, residual = ops._f32c(x), _opt(residual)
     g, b = _vec(gamma), _vec(beta)                                # bound until the launch is enqueued
     head = weight = bias = None
     if gate is not None:
@@ -87,12 +81,9 @@ def groupnorm_relu_backward(grad_y, x, stats, groups, gamma=None, beta=None, res
     where ``want`` (five flags; default: all, grad_residual with a residual, dgain with a gain) is false.  ``out``: a dict of caller buffers by
     those names."""
     grad_y, x, stats = ops._f32c(grad_y), ops._f32c(x), ops._f32c(stats)
-    residual = ops._f32c(residual) if residual is not None else None
-    gain = ops._f32c(gain) if gain is not None else None
+    residual, gain = _opt(residual), _opt(gain)
     g, b = _vec(gamma), _vec(beta)                                # bound until the launch is enqueued
     out = dict(out or {})
-    if set(out) - set(_GN_OUTS):
-        raise ValueError(f"groupnorm_relu_backward: unknown outputs {sorted(set(out) - set(_GN_OUTS))}")
     ops._need_gpu(grad_y, x, stats, residual, gain, g, b, *out.values())
     N, C, hw = _gn_shape("groupnorm_relu_backward", x, groups)
     groups = int(groups)
@@ -102,20 +93,14 @@ def groupnorm_relu_backward(grad_y, x, stats, groups, gamma=None, beta=None, res
         raise ValueError(f"groupnorm_relu_backward: stats must hold {N * groups} (mean, rstd) pairs, gain {N * C} and gamma, beta {C} elements")
     if want is None:
         want = (True, residual is not None, True, True, gain is not None)
-    shapes = (tuple(x.shape), tuple(x.shape), (C,), (C,), (N, C))
-    bufs = []
-    for name, shape, w in zip(_GN_OUTS, shapes, want):
-        if name in out:
-            bufs.append(ops._out("groupnorm_relu_backward: " + name, out[name], shape))
-        else:
-            bufs.append(torch.empty(shape, dtype=torch.float32, device=x.device) if w else None)
+    bufs = _wanted("groupnorm_relu_backward", _GN_OUTS, (tuple(x.shape), tuple(x.shape), (C,), (C,), (N, C)), want, out, x)
     grad_x, grad_residual, grad_gamma, grad_beta, dgain = bufs
     L = _lib.lib()
     ws = ops._ws(L.aoc_groupnorm_relu_grad_workspace_bytes(N, C, groups), x.device)
     _lib.check(L.aoc_groupnorm_relu_grad(ops._p(grad_y), ops._p(x), ops._p(residual), ops._p(stats), ops._p(g), ops._p(b), ops._p(gain), N, C, hw, groups,
                                          int(bool(relu)), ops._p(grad_x), ops._p(grad_residual), ops._p(grad_gamma), ops._p(grad_beta), ops._p(dgain),
                                          ops._p(ws), ws.numel(), ops._stream()), "aoc_groupnorm_relu_grad")
-    return tuple(bufs)
+    return bufs
 
 
 def cat_film_scale_backward(grad_y, x=None, mem=None, gain=None, grad_x=None, grad_mem=None, dgain=None, want_x=True, want_mem=False, want_gain=True):
@@ -123,9 +108,7 @@ def cat_film_scale_backward(grad_y, x=None, mem=None, gain=None, grad_x=None, gr
     (grad_x = gain[:, :Cx] grad_y[:, :Cx], grad_mem likewise for the memory's channels, dgain = the plane dots of grad_y with [x | mem]);
     None where not wanted.  x and mem are read for dgain only, and only their shapes otherwise."""
     grad_y = ops._f32c(grad_y)
-    x = ops._f32c(x) if x is not None else None
-    mem = ops._f32c(mem) if mem is not None else None
-    gain = ops._f32c(gain) if gain is not None else None
+    x, mem, gain = _opt(x), _opt(mem), _opt(gain)
     ops._need_gpu(grad_y, x, mem, gain, grad_x, grad_mem, dgain)
     want_x, want_mem, want_gain = bool(want_x or grad_x is not None), bool(want_mem or grad_mem is not None), bool(want_gain or dgain is not None)
     if grad_y.dim() < 2 or grad_y.numel() == 0 or x is None or x.dim() != grad_y.dim():
@@ -152,10 +135,6 @@ def cat_film_scale_backward(grad_y, x=None, mem=None, gain=None, grad_x=None, gr
 
 
 # ------------------------------------------------------------------------------------------ the fused forms
-def _det(t):
-    return ops._f32c(t.detach()) if t is not None else None
-
-
 class _GroupNormRelu(torch.autograd.Function):
     """x, residual [N, C, ...], gamma, beta [C] -> [relu](GroupNorm(x) gamma + beta [+ residual]) by aoc_groupnorm_relu; saves x, the residual
     and the statistics."""

@@ -26,7 +26,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib, attention, cluster_train, local_train, matching, matching_train, ops
 from .matching import DEFAULT_CLUSTER_NUM
-from .matching_train import _wants_grad
+from .ops import _wants_grad
 
 
 # ------------------------------------------------------------------------------------------ the C ABI

@@ -19,39 +19,27 @@ forward kernel's own dot product: the two differ in summation order only, and th
 ``phi_layer`` gets NO gradient: the reference compares the scores (``x > beta_val[..., -1, None]``, CLB:36), so its autograd leaves
 ``phi_layer.weight.grad`` and ``phi_layer.bias.grad`` at ``None``; so do these twins.
 
-Without a wanted gradient (``matching_train._wants_grad``) every twin returns the mirror's result through the mirror's own ``ops`` calls;
+Without a wanted gradient (``ops._wants_grad``) every twin returns the mirror's result through the mirror's own ``ops`` calls;
 with one, the forward calls the same entry points, so the output bits are the mirror's.  Frozen parameters and ``ctx.needs_input_grad``
 select which optional outputs the kernels are asked for.  All backwards are ``once_differentiable``.  Every sum runs in a fixed order without
 float atomics: two runs give the same bits.  The ctypes wrappers of the new entry points live here, not in ``ops`` (whose public names are
-a tested table); they keep ``ops``' tensor contract: inputs converted by ``_f32c`` into names that live until the call, caller outputs
-checked by ``_out``, addresses only through ``_p``.
+a tested table); they keep ``ops``' tensor contract through its helpers: inputs converted by ``_f32c`` / ``_opt`` into names that live until the
+call, caller outputs checked by ``_out`` (the named optional ones chosen by ``_wanted``), addresses only through ``_p``.
 """
 import torch
 from torch import nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib, ops
-from .matching_train import _wants_grad
+from .ops import _det, _new, _opt, _planes_hw, _wanted, _wants_grad
 
 
 # ------------------------------------------------------------------------------------------ the C ABI
-def _planes_hw(what, x):
-    if x.dim() < 2 or x.numel() == 0:
-        raise ValueError(f"{what}: expected a non-empty [N, C, ...] tensor, got {tuple(x.shape)}")
-    planes = x.shape[0] * x.shape[1]
-    return planes, x.numel() // planes
-
-
-def _new(like, *shape):
-    return torch.empty(*shape, dtype=torch.float32, device=like.device)
-
-
 def channel_scale_backward(grad_y, x=None, gain=None, grad_x=None, dgain=None, want_x=True, want_gain=True):
     """aoc_channel_scale_grad: grad_y, x [N, C, ...], gain [N, C] -> (grad_x = gain * grad_y, dgain [N, C] = plane dots of grad_y and x);
     None where not wanted.  x may be None without want_gain, gain without want_x."""
     grad_y = ops._f32c(grad_y)
-    x = ops._f32c(x) if x is not None else None
-    gain = ops._f32c(gain) if gain is not None else None
+    x, gain = _opt(x), _opt(gain)
     ops._need_gpu(grad_y, x, gain, grad_x, dgain)
     planes, hw = _planes_hw("channel_scale_backward", grad_y)
     want_x, want_gain = bool(want_x or grad_x is not None), bool(want_gain or dgain is not None)
@@ -77,11 +65,8 @@ def film_gain_backward(dgain, gain, head, weight, grad_head=None, grad_weight=No
     if gain.shape != dgain.shape or tuple(head.shape) != (n_obj, D) or tuple(weight.shape) != (channels, D):
         raise ValueError(f"film_gain_backward: gain {tuple(gain.shape)}, head {tuple(head.shape)}, weight {tuple(weight.shape)} do not fit dgain "
                          f"{tuple(dgain.shape)}")
-    outs = []
-    for name, buf, shape, w in (("grad_head", grad_head, (n_obj, D), want[0]), ("grad_weight", grad_weight, (channels, D), want[1]),
-                                ("grad_bias", grad_bias, (channels,), want[2])):
-        outs.append(ops._out("film_gain_backward: " + name, buf, shape) if buf is not None else (_new(dgain, *shape) if w else None))
-    grad_head, grad_weight, grad_bias = outs
+    grad_head, grad_weight, grad_bias = _wanted("film_gain_backward", ("grad_head", "grad_weight", "grad_bias"), ((n_obj, D), (channels, D), (channels,)),
+                                                want, dict(grad_head=grad_head, grad_weight=grad_weight, grad_bias=grad_bias), dgain)
     _lib.check(_lib.lib().aoc_film_gain_grad(ops._p(dgain), ops._p(gain), ops._p(head), ops._p(weight), n_obj, D, channels, ops._p(grad_head),
                                              ops._p(grad_weight), ops._p(grad_bias), ops._stream()), "aoc_film_gain_grad")
     return grad_head, grad_weight, grad_bias
@@ -97,11 +82,8 @@ def gct_gate_backward(dgate, gate, plane_sums, alpha, gamma, beta, eps, l1_mode=
     if dgate.dim() != 2 or gate.shape != dgate.shape or plane_sums.shape != dgate.shape or not (al.numel() == ga.numel() == be.numel() == dgate.shape[1]):
         raise ValueError(f"gct_gate_backward: gate, plane_sums must be [N, C] = {tuple(dgate.shape)} and alpha, gamma, beta hold C elements")
     N, C = dgate.shape
-    outs = []
-    for name, buf, shape, w in (("dsum", dsum, (N, C), want[0]), ("grad_alpha", grad_alpha, (C,), want[1]), ("grad_gamma", grad_gamma, (C,), want[2]),
-                                ("grad_beta", grad_beta, (C,), want[3])):
-        outs.append(ops._out("gct_gate_backward: " + name, buf, shape) if buf is not None else (_new(dgate, *shape) if w else None))
-    dsum, grad_alpha, grad_gamma, grad_beta = outs
+    dsum, grad_alpha, grad_gamma, grad_beta = _wanted("gct_gate_backward", ("dsum", "grad_alpha", "grad_gamma", "grad_beta"), ((N, C), (C,), (C,), (C,)), want,
+                                                      dict(dsum=dsum, grad_alpha=grad_alpha, grad_gamma=grad_gamma, grad_beta=grad_beta), dgate)
     _lib.check(_lib.lib().aoc_gct_gate_grad(ops._p(dgate), ops._p(gate), ops._p(plane_sums), ops._p(al), ops._p(ga), ops._p(be), N, C, float(eps),
                                             int(bool(l1_mode)), ops._p(dsum), ops._p(grad_alpha), ops._p(grad_gamma), ops._p(grad_beta), ops._stream()),
                "aoc_gct_gate_grad")
@@ -130,7 +112,7 @@ def cond_codes_backward(dcode, gap, plane_means, head, w1, w2, w3, want=(True,) 
     grad_w1, grad_b1, grad_w2, grad_b2, grad_w3, grad_b3); None where ``want`` is false.  ``out``: a dict of caller buffers by those names.
     With C = 0 (gap, plane_means, w1, w2 = None) the third code alone is the backward of one square ``ops.linear``."""
     dcode, head, w3 = ops._f32c(dcode), ops._f32c(head), ops._f32c(w3)
-    gap, plane_means, w1, w2 = (ops._f32c(t) if t is not None else None for t in (gap, plane_means, w1, w2))
+    gap, plane_means, w1, w2 = _opt(gap), _opt(plane_means), _opt(w1), _opt(w2)
     out = dict(out or {})
     ops._need_gpu(dcode, gap, plane_means, head, w1, w2, w3, *out.values())
     if dcode.dim() != 2 or head.dim() != 2:
@@ -142,26 +124,19 @@ def cond_codes_backward(dcode, gap, plane_means, head, w1, w2, w3, want=(True,) 
     if have != need:
         raise ValueError(f"cond_codes_backward: dcode, gap, plane_means, w1, w2, w3 must have shapes {need}, got {have}")
     shapes = ((N, C), (N, C), (N, D), (C, C), (C,), (C, C), (C,), (D, D), (D,))
-    if set(out) - set(_CODE_OUTS):
-        raise ValueError(f"cond_codes_backward: unknown outputs {sorted(set(out) - set(_CODE_OUTS))}")
-    bufs = []
-    for name, shape, w in zip(_CODE_OUTS, shapes, want):
-        if name in out:
-            bufs.append(ops._out("cond_codes_backward: " + name, out[name], shape))
-        else:
-            bufs.append(_new(dcode, *shape) if (w and shape[0] > 0 and shape[-1] > 0) else None)
+    bufs = _wanted("cond_codes_backward", _CODE_OUTS, shapes, want, out, dcode)
     dgap, dpx, grad_head, grad_w1, grad_b1, grad_w2, grad_b2, grad_w3, grad_b3 = bufs
     _lib.check(_lib.lib().aoc_cond_codes_grad(ops._p(dcode), ops._p(gap), ops._p(plane_means), ops._p(head), ops._p(w1), ops._p(w2), ops._p(w3), N, C, D,
                                               ops._p(dgap), ops._p(dpx), ops._p(grad_head), ops._p(grad_w1), ops._p(grad_b1), ops._p(grad_w2),
                                               ops._p(grad_b2), ops._p(grad_w3), ops._p(grad_b3), ops._stream()), "aoc_cond_codes_grad")
-    return tuple(bufs)
+    return bufs
 
 
 def cond_scale_backward(grad_y, gain, scores, threshold, dgap, dpx, shape=None, grad_x=None):
     """aoc_cond_scale_grad: grad_x[n, c, p] = grad_y gain[n, c] + (scores[n, p] > threshold[n] ? dgap[n, c] : 0) / hw + dpx[n, c] / hw.  grad_y (with
     gain), dgap and dpx may each be None; ``shape`` = (N, C, ...) of grad_x is needed when grad_y is None."""
     scores, threshold = ops._f32c(scores), ops._f32c(threshold).reshape(-1)
-    grad_y, gain, dgap, dpx = (ops._f32c(t) if t is not None else None for t in (grad_y, gain, dgap, dpx))
+    grad_y, gain, dgap, dpx = _opt(grad_y), _opt(gain), _opt(dgap), _opt(dpx)
     ops._need_gpu(grad_y, gain, scores, threshold, dgap, dpx, grad_x)
     shape = tuple(grad_y.shape if grad_y is not None else shape)
     if len(shape) < 2 or scores.dim() != 2:
@@ -186,7 +161,7 @@ class _FilmScale(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, head, weight, bias):
         xd, hd, wd = ops._f32c(x.detach()), ops._f32c(head.detach()), ops._f32c(weight.detach())
-        bd = ops._f32c(bias.detach()) if bias is not None else None
+        bd = _det(bias)
         gain = ops.film_gain(hd, wd, bd)
         ctx.save_for_backward(xd, hd, wd, gain)
         return ops.film_scale(xd, hd, wd, bd)

@@ -24,8 +24,9 @@ import torch
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
-from . import _lib, matching, ops
-from .matching_train import _bias_arg, _wants_grad
+from . import matching, ops
+from .matching_train import _bias_arg, _guard
+from .ops import _wants_grad
 
 
 class _LocalMatch(torch.autograd.Function):
@@ -62,10 +63,7 @@ def local_matching(prev_frame_embedding, query_embedding, prev_frame_labels, dis
     if not _wants_grad(prev_frame_embedding, query_embedding, dis_bias):
         return matching.local_matching(prev_frame_embedding, query_embedding, prev_frame_labels, dis_bias, multi_local_distance, ori_size,
                                        atrous_rate, use_float16, allow_downsample, allow_parallel)
-    if use_float16:
-        raise _lib.AocHipError("aoc_amd.local_train.local_matching: use_float16=True has no backward (the `.half()` matching mode is inference-only); "
-                               "pass use_float16=False, as the model does with MODEL_FLOAT16_MATCHING = False")
-    ops._need_gpu(*[t for t in (prev_frame_embedding, query_embedding, prev_frame_labels, dis_bias) if torch.is_tensor(t)])
+    _guard("local_matching", use_float16, prev_frame_embedding, query_embedding, prev_frame_labels, dis_bias, module="local_train")
     h, w, _ = prev_frame_embedding.size()
     ori_size = (h, w) if ori_size is None else (int(ori_size[0]), int(ori_size[1]))
     obj_num = prev_frame_labels.size(2)

@@ -28,7 +28,7 @@ from torch import nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib, ops
-from .matching_train import _wants_grad
+from .ops import _wanted, _wants_grad
 
 IGNORE_INDEX = 255
 MAX_CHANNELS = 31
@@ -77,12 +77,6 @@ def _word(what, t, dtype=torch.float32):
     return _plane(what, t, 1, dtype)
 
 
-def _maybe(what, t, want, n, dtype, device):
-    if t is not None:
-        return ops._out(what, t, (n,), dtype)
-    return torch.empty(n, dtype=dtype, device=device) if want else None
-
-
 _FWD_OUTS = ("loss", "lse", "argmax", "valid_partial", "bad")
 
 
@@ -96,17 +90,14 @@ def upsample_ce_forward(pred, labels, size, ignore_index=IGNORE_INDEX, want=(Tru
     n = H * W
     lab = _labels(what, labels, n)                               # bound until the launch is enqueued
     out = dict(out or {})
-    if set(out) - set(_FWD_OUTS):
-        raise ValueError(f"{what}: unknown outputs {sorted(set(out) - set(_FWD_OUTS))}")
     L = _lib.lib()
-    sizes = (n, n, n, int(L.aoc_upsample_ce_partials(n)), 1)
-    dtypes = (torch.float32, torch.float32, torch.int32, torch.int32, torch.int32)
+    shapes = ((n,), (n,), (n,), (int(L.aoc_upsample_ce_partials(n)),), (1,))
     ops._need_gpu(pred, lab, *out.values())
-    bufs = [_maybe(f"{what}: {name}", out.get(name), w, m, dt, pred.device) for name, w, m, dt in zip(_FWD_OUTS, want, sizes, dtypes)]
+    bufs = _wanted(what, _FWD_OUTS, shapes, want, out, pred, (torch.float32, torch.float32, torch.int32, torch.int32, torch.int32))
     C, h, w = pred.shape
     _lib.check(L.aoc_upsample_ce_forward(ops._p(pred), ops._p(lab), C, h, w, H, W, int(ignore_index), *(ops._p(b) for b in bufs), ops._stream()),
                "aoc_upsample_ce_forward")
-    return tuple(bufs)
+    return bufs
 
 
 def _check_k(what, k, n):
@@ -125,9 +116,8 @@ def topk_mean(loss, k, mean=None, thr=None, n_gt=None, want=(True, True, True)):
         raise ValueError("topk_mean: an empty loss")
     k = _check_k("topk_mean", k, n)
     ops._need_gpu(loss, mean, thr, n_gt)
-    mean = _maybe("topk_mean: mean", mean, want[0], 1, torch.float32, loss.device)
-    thr = _maybe("topk_mean: thr", thr, want[1], 1, torch.float32, loss.device)
-    n_gt = _maybe("topk_mean: n_gt", n_gt, want[2], 1, torch.int32, loss.device)
+    mean, thr, n_gt = _wanted("topk_mean", ("mean", "thr", "n_gt"), ((1,),) * 3, want, dict(mean=mean, thr=thr, n_gt=n_gt), loss,
+                              (torch.float32, torch.float32, torch.int32))
     L = _lib.lib()
     ws = ops._ws(L.aoc_topk_mean_workspace_bytes(n), loss.device)
     _lib.check(L.aoc_topk_mean(ops._p(loss), n, k, ops._p(mean), ops._p(thr), ops._p(n_gt), ops._p(ws), ws.numel(), ops._stream()), "aoc_topk_mean")
@@ -141,8 +131,7 @@ def valid_mean(loss, valid_partial, mean=None, n_valid=None):
     L = _lib.lib()
     valid_partial = _plane("valid_mean: valid_partial", valid_partial, int(L.aoc_upsample_ce_partials(n)) if n else -1, torch.int32)
     ops._need_gpu(loss, valid_partial, mean, n_valid)
-    mean = _maybe("valid_mean: mean", mean, True, 1, torch.float32, loss.device)
-    n_valid = _maybe("valid_mean: n_valid", n_valid, True, 1, torch.int32, loss.device)
+    mean, n_valid = _wanted("valid_mean", ("mean", "n_valid"), ((1,),) * 2, (True, True), dict(mean=mean, n_valid=n_valid), loss, (torch.float32, torch.int32))
     ws = ops._ws(L.aoc_topk_mean_workspace_bytes(n), loss.device)
     _lib.check(L.aoc_valid_mean(ops._p(loss), n, ops._p(valid_partial), valid_partial.numel(), ops._p(mean), ops._p(n_valid), ops._p(ws), ws.numel(),
                                 ops._stream()), "aoc_valid_mean")
@@ -158,7 +147,7 @@ def topk_select_mask(loss, k, thr, n_gt, mask=None):
     k = _check_k("topk_select_mask", k, n)
     thr, n_gt = _word("topk_select_mask: thr", thr), _word("topk_select_mask: n_gt", n_gt, torch.int32)
     ops._need_gpu(loss, thr, n_gt, mask)
-    mask = _maybe("topk_select_mask: mask", mask, True, n, torch.uint8, loss.device)
+    mask, = _wanted("topk_select_mask", ("mask",), ((n,),), (True,), dict(mask=mask), loss, (torch.uint8,))
     L = _lib.lib()
     ws = ops._ws(L.aoc_topk_select_mask_workspace_bytes(n), loss.device)
     _lib.check(L.aoc_topk_select_mask(ops._p(loss), n, k, ops._p(thr), ops._p(n_gt), ops._p(mask), ops._p(ws), ws.numel(), ops._stream()),
@@ -175,7 +164,7 @@ def valid_mask(labels, channels, ignore_index=IGNORE_INDEX, mask=None):
     if not 1 <= int(channels) <= MAX_CHANNELS:
         raise ValueError(f"valid_mask: {channels} channels (1 to {MAX_CHANNELS})")
     ops._need_gpu(lab, mask)
-    mask = _maybe("valid_mask: mask", mask, True, n, torch.uint8, lab.device)
+    mask, = _wanted("valid_mask", ("mask",), ((n,),), (True,), dict(mask=mask), lab, (torch.uint8,))
     _lib.check(_lib.lib().aoc_valid_mask(ops._p(lab), n, int(channels), int(ignore_index), ops._p(mask), ops._stream()), "aoc_valid_mask")
     return mask
 

@@ -21,15 +21,13 @@ import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
 from . import _lib, matching, ops
+from .ops import _wants_grad
 
 
-def _wants_grad(*tensors):
-    return torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in tensors)
-
-
-def _guard(what, use_float16, *tensors):
+def _guard(what, use_float16, *tensors, module="matching_train", why="the `.half()` matching mode is inference-only"):
+    """The float16 refusal and the device check of a differentiable matching; ``module`` and ``why`` fill local_train's and cluster_train's texts."""
     if use_float16:
-        raise _lib.AocHipError(f"aoc_amd.matching_train.{what}: use_float16=True has no backward (the `.half()` matching mode is inference-only); "
+        raise _lib.AocHipError(f"aoc_amd.{module}.{what}: use_float16=True has no backward ({why}); "
                                "pass use_float16=False, as the model does with MODEL_FLOAT16_MATCHING = False")
     ops._need_gpu(*[t for t in tensors if torch.is_tensor(t)])
 

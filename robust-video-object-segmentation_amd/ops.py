@@ -153,6 +153,57 @@ def _ws(nbytes, device):
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
 
+# The helpers of the ctypes wrappers that live in the *_train modules (their entry points are not in this module's tested table of public
+# names); one copy, here, beside the contract they keep.
+def _wants_grad(*tensors):
+    return torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in tensors)
+
+
+def _opt(t):
+    """_f32c of an optional input (None stays None)."""
+    return _f32c(t) if t is not None else None
+
+
+def _vec(t):
+    """An optional parameter of any shape as a flat float32 vector."""
+    return _f32c(t).reshape(-1) if t is not None else None
+
+
+def _det(t):
+    """What an autograd Function hands to the wrappers and saves: the optional input detached, float32, contiguous."""
+    return _f32c(t.detach()) if t is not None else None
+
+
+def _new(like, *shape, dtype=torch.float32):
+    return torch.empty(*shape, dtype=dtype, device=like.device)
+
+
+def _planes_hw(what, x):
+    """x [N, C, ...] -> (N * C planes, elements per plane)."""
+    if x.dim() < 2 or x.numel() == 0:
+        raise ValueError(f"{what}: expected a non-empty [N, C, ...] tensor, got {tuple(x.shape)}")
+    planes = x.shape[0] * x.shape[1]
+    return planes, x.numel() // planes
+
+
+def _wanted(what, names, shapes, want, out, like, dtypes=None):
+    """The named optional outputs of a backward entry -> a tuple in the order of ``names``.  For each name, in this order: the caller's
+    buffer ``out[name]`` checked by _out (a caller buffer is always written, whatever its ``want`` flag says); a fresh tensor on ``like``'s
+    device if wanted and every extent is positive; else None (the library skips an output whose pointer is null).  ``out``: a dict by those
+    names, None entries count as absent; a name outside ``names`` raises ValueError."""
+    out = out or {}
+    if set(out) - set(names):
+        raise ValueError(f"{what}: unknown outputs {sorted(set(out) - set(names))}")
+    bufs = []
+    for k, (name, shape, w) in enumerate(zip(names, shapes, want)):
+        dtype = dtypes[k] if dtypes else torch.float32
+        if out.get(name) is not None:
+            bufs.append(_out(f"{what}: {name}", out[name], shape, dtype))
+        else:
+            bufs.append(_new(like, *shape, dtype=dtype) if w and all(s > 0 for s in shape) else None)
+    return tuple(bufs)
+
+
 # ------------------------------------------------------------------------------------------ labels
 def label_bits(labels_flat, want_wrong=True):
     """labels [n, O] float -> (right_bits, wrong_bits) uint32-as-int32 tensors [n]."""
@@ -298,7 +349,7 @@ def proxy_corr_min(query_flat, proxies, proxy_sqnorm, set_begin, set_size, set_o
     (aoc_proxy_corr_min_f16)."""
     query_flat = _f32c(query_flat)
     proxies = _a16("proxy_corr_min: proxies", _f32c(proxies))
-    proxy_sqnorm = _f32c(proxy_sqnorm) if proxy_sqnorm is not None else None
+    proxy_sqnorm = _opt(proxy_sqnorm)
     _need_gpu(query_flat, proxies, proxy_sqnorm, out, set_bias)
     m, C = query_flat.shape
     sb = np.ascontiguousarray(np.asarray(set_begin, dtype=np.int32))
@@ -359,8 +410,8 @@ def proxy_corr_min_batched(frames, set_begin, set_size, set_out_offset, transfor
     keep = []
     for i, (q, p, sq, b, out) in enumerate(frames):
         q, p = _a16("proxy_corr_min_batched: query", _f32c(q)), _a16("proxy_corr_min_batched: proxies", _f32c(p))
-        sq = _f32c(sq) if sq is not None else None
-        b = _f32c(b) if b is not None else None
+        sq = _opt(sq)
+        b = _opt(b)
         _need_gpu(q, p, sq, b, out)
         assert q.shape == (m, C) and p.shape == (n_proxy, C) and (b is None or b.numel() == n_set)
         _span("proxy_corr_min_batched: out", out, int(so.max()) + m if n_set else 0)
@@ -400,8 +451,8 @@ def proxy_corr_min_records(frames, set_begin, set_size, set_out_offset, transfor
     keep = []
     for i, (q, qs, p, sq, b, out) in enumerate(frames):
         q, p = _f32c(q), _a16("proxy_corr_min_records: proxies", _f32c(p))
-        sq = _f32c(sq) if sq is not None else None
-        b = _f32c(b) if b is not None else None
+        sq = _opt(sq)
+        b = _opt(b)
         _need_gpu(q, p, sq, b, out, qs.records, qs.sqnorm)
         assert qs.tiled and qs.n == m, "the records kernel reads aoc_split_rows_tiled records of the whole query"
         assert q.shape == (m, C) and p.shape == (n_proxy, C) and (b is None or b.numel() == n_set)
@@ -556,7 +607,7 @@ def proxy_set_match_argmin(query_flat, proxies, proxy_sqnorm, set_begin, set_siz
     set of every minimum (ties: the lowest); -1 where the set is empty or all-ignored."""
     query_flat = _f32c(query_flat)
     proxies = _f32c(proxies)
-    proxy_sqnorm = _f32c(proxy_sqnorm) if proxy_sqnorm is not None else None
+    proxy_sqnorm = _opt(proxy_sqnorm)
     _need_gpu(query_flat, proxies, proxy_sqnorm, out, arg, set_bias)
     m, C = query_flat.shape
     sb, ss, so = _set_arrays(set_begin, set_size, set_out_offset)
@@ -1257,7 +1308,7 @@ def masked_mean_pool(emb, labels, epsilon, pixel_major=False, out_pos=None, out_
 
 def film_gain(head, weight, bias):
     head, weight = _f32c(head), _f32c(weight)
-    bias = _f32c(bias) if bias is not None else None
+    bias = _opt(bias)
     _need_gpu(head, weight, bias)
     n_obj, D = head.shape
     channels = weight.shape[0]
@@ -1282,7 +1333,7 @@ def channel_scale(x, gain, out=None):
 def film_scale(x, head, weight, bias, out=None):
     """y[o,c,:,:] = (1 + tanh(head[o,:] . weight[c,:] + bias[c])) * x[o,c,:,:] in one launch (ATT:12-17, CLB:81-84)."""
     x, head, weight = _f32c(x), _f32c(head), _f32c(weight)
-    bias = _f32c(bias) if bias is not None else None
+    bias = _opt(bias)
     _need_gpu(x, head, weight, bias)
     n_obj, channels = x.shape[0], x.shape[1]
     assert head.shape[0] == n_obj and weight.shape[0] == channels and weight.shape[1] == head.shape[1]
@@ -1305,8 +1356,8 @@ def cat_film_scale(x, mem, head, weight, bias, out=None):
     """torch.cat([x, mem], 1) gated by IA_gate in one launch (decoding_module.py:193-194, 203-204): bit-equal to
     ``film_scale(torch.cat([x, mem], 1), head, weight, bias)``.  mem may be x itself (first frame) or None (plain film_scale)."""
     x, head, weight = _f32c(x), _f32c(head), _f32c(weight)
-    mem = _f32c(mem) if mem is not None else None
-    bias = _f32c(bias) if bias is not None else None
+    mem = _opt(mem)
+    bias = _opt(bias)
     n_obj, Cx = x.shape[0], x.shape[1]
     Cm = mem.shape[1] if mem is not None else 0
     if mem is not None and (mem.shape[0] != n_obj or mem.shape[2:] != x.shape[2:]):
@@ -1345,7 +1396,7 @@ def cond_gate_pool(z, phi_w, phi_b, k_rank, want_debug=False, want_plane_mean=Fa
 
 def linear(x, weight, bias):
     x, weight = _f32c(x), _f32c(weight)
-    bias = _f32c(bias) if bias is not None else None
+    bias = _opt(bias)
     _need_gpu(x, weight, bias)
     N, in_dim = x.shape
     out_dim = weight.shape[0]
@@ -1505,7 +1556,7 @@ def plane_reduce(x, mode):
 def groupnorm_relu(x, groups, gamma, beta, eps=1e-5, residual=None, relu=True, out=None):
     """aoc_groupnorm_relu: [relu](GroupNorm(x) [+ residual]) in two streams over x (gct.py:69-90)."""
     x = _f32c(x)
-    residual = _f32c(residual) if residual is not None else None
+    residual = _opt(residual)
     _need_gpu(x, gamma, beta, residual)
     N, C = x.shape[0], x.shape[1]
     hw = x.numel() // (N * C)
@@ -1514,8 +1565,8 @@ def groupnorm_relu(x, groups, gamma, beta, eps=1e-5, residual=None, relu=True, o
     _need_gpu(out)
     ws = _ws(L.aoc_groupnorm_relu_workspace_bytes(N, int(groups)), x.device)
     # converted copies stay bound until the launch is enqueued: a temporary freed right after data_ptr() can be handed out again by the allocator
-    g = _f32c(gamma) if gamma is not None else None
-    b = _f32c(beta) if beta is not None else None
+    g = _opt(gamma)
+    b = _opt(beta)
     _lib.check(L.aoc_groupnorm_relu(_p(x), N, C, hw, int(groups), _p(g), _p(b),
                                     float(eps), _p(residual), int(bool(relu)), _p(y), _p(ws), ws.numel(), _stream()), "aoc_groupnorm_relu")
     return y
@@ -1525,8 +1576,8 @@ def groupnorm_relu_scale(x, groups, gamma, beta, eps, residual, relu, head, weig
     """aoc_groupnorm_relu_scale: groupnorm_relu with the IA_gate that follows folded into its apply pass; bit-equal to
     ``film_scale(groupnorm_relu(x, groups, gamma, beta, eps, residual, relu), head, weight, gate_bias)``."""
     x, head, weight = _f32c(x), _f32c(head), _f32c(weight)
-    residual = _f32c(residual) if residual is not None else None
-    gate_bias = _f32c(gate_bias) if gate_bias is not None else None
+    residual = _opt(residual)
+    gate_bias = _opt(gate_bias)
     N, C = x.shape[0], x.shape[1]
     if int(groups) < 1 or C % int(groups):
         raise ValueError(f"groupnorm_relu_scale: {C} channels do not divide into {groups} groups")
@@ -1537,8 +1588,8 @@ def groupnorm_relu_scale(x, groups, gamma, beta, eps, residual, relu, head, weig
     y = torch.empty_like(x) if out is None else _out("groupnorm_relu_scale: out", out, x.shape)
     _need_gpu(out)
     ws = _ws(L.aoc_groupnorm_relu_workspace_bytes(N, int(groups)), x.device)
-    g = _f32c(gamma) if gamma is not None else None              # bound until the launch is enqueued (see groupnorm_relu)
-    b = _f32c(beta) if beta is not None else None
+    g = _opt(gamma)              # bound until the launch is enqueued (see groupnorm_relu)
+    b = _opt(beta)
     _lib.check(L.aoc_groupnorm_relu_scale(_p(x), N, C, hw, int(groups), _p(g), _p(b), float(eps), _p(residual), int(bool(relu)), _p(head), _p(weight),
                                           _p(gate_bias), head.shape[1], _p(y), _p(ws), ws.numel(), _stream()), "aoc_groupnorm_relu_scale")
     return y
@@ -1694,8 +1745,8 @@ def bicubic_cat_scale(x, low=None, gain=None, size=None, out=None):
     (decoding_module.py:163, :170 and the scaling of ATT:15-16).  x [N, Ce, h, w]; low [N, Cr, H, W] or None (size gives H, W then);
     gain [N, Ce + Cr] or None (= 1)."""
     x = _f32c(x)
-    low = _f32c(low) if low is not None else None
-    gain = _f32c(gain) if gain is not None else None
+    low = _opt(low)
+    gain = _opt(gain)
     _need_gpu(x, low, gain)
     N, Ce, h, w = x.shape
     Cr = low.shape[1] if low is not None else 0
@@ -1715,7 +1766,7 @@ def shortcut_stage(x, low, IA_head, weight, bias, want_debug=False, out=None):
     Linear given as weight [Ce + Cr, D + Ce + Cr], bias.  x [N, Ce, h, w], low [N, Cr, H, W] (the shortcut branch after its ReLU),
     IA_head [N, D].  want_debug: also the plane means and the gain, both [N, Ce + Cr]."""
     x, low, IA_head, weight = _f32c(x), _f32c(low), _f32c(IA_head), _f32c(weight)
-    bias = _f32c(bias) if bias is not None else None
+    bias = _opt(bias)
     _need_gpu(x, low, IA_head, weight, bias)
     N, Ce, h, w = x.shape
     Cr, H, W = low.shape[1:]

@@ -13,15 +13,16 @@ embedding's gradient is the cotangent's first C channels summed over the objects
 Without a wanted gradient the module returns the mirror's result through ``ops.prehead``; with one, the forward calls the same C entry
 (``aoc_prehead``), so the output bits are the mirror's.  Frozen parameters and ``ctx.needs_input_grad`` select which optional outputs the
 kernels are asked for.  The backward is ``once_differentiable``; every sum runs in a fixed order without float atomics.  The ctypes wrappers
-live here, not in ``ops`` (whose public names are a tested table); they keep ``ops``' tensor contract: inputs converted by ``_f32c`` into
-names that live until the call, caller outputs checked by ``_out``, addresses only through ``_p``.
+live here, not in ``ops`` (whose public names are a tested table); they keep ``ops``' tensor contract through its helpers: inputs converted by
+``_f32c`` / ``_opt`` / ``_vec`` into names that live until the call, caller outputs checked by ``_out`` (the named optional ones chosen by
+``_wanted``), addresses only through ``_p``.
 """
 import torch
 from torch import nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib, ops
-from .matching_train import _wants_grad
+from .ops import _det, _opt, _vec, _wanted, _wants_grad
 
 PIX = 256                                   # pixels per chunk of aoc_prehead / aoc_prehead_grad (PH_PIX)
 OUTS = ("grad_feat", "grad_weight", "grad_bias", "grad_gamma", "grad_beta", "grad_emb")
@@ -41,16 +42,12 @@ def _shapes(what, feat, weight, n_groups):
     return O, n_in, n_out, hw
 
 
-def _vec(t):
-    return ops._f32c(t).reshape(-1)
-
-
 def prehead_forward(feat, weight, bias, n_groups, gamma, beta, eps, emb_hwc=None):
     """ops.prehead keeping the statistics: feat [O, n_in, h, w] -> (out [O, C + n_out, h, w], stats [O * n_groups, 2] = (mean, rstd), a view of
     the call's workspace).  The same C entry as the mirror's wrapper, so out has its bits."""
     feat, weight = ops._f32c(feat), ops._f32c(weight)
     bi, g, b = _vec(bias), _vec(gamma), _vec(beta)                # bound until the launch is enqueued
-    emb_hwc = ops._f32c(emb_hwc) if emb_hwc is not None else None
+    emb_hwc = _opt(emb_hwc)
     if feat.dim() != 4:
         raise ValueError(f"prehead_forward: expected feat [O, n_in, h, w], got {tuple(feat.shape)}")
     O, n_in, n_out, hw = _shapes("prehead_forward", feat, weight, n_groups)
@@ -80,8 +77,6 @@ def prehead_backward(grad_out, feat, stats, weight, bias, n_groups, gamma, beta,
     grad_out, feat, stats, weight = ops._f32c(grad_out), ops._f32c(feat), ops._f32c(stats), ops._f32c(weight)
     bi, g, b = _vec(bias), _vec(gamma), _vec(beta)                # bound until the launch is enqueued
     out = dict(out or {})
-    if set(out) - set(OUTS):
-        raise ValueError(f"prehead_backward: unknown outputs {sorted(set(out) - set(OUTS))}")
     ops._need_gpu(grad_out, feat, stats, weight, bi, g, b, *out.values())
     O, n_in, n_out, hw = _shapes("prehead_backward", feat, weight, n_groups)
     n_groups, C = int(n_groups), int(C)
@@ -97,24 +92,15 @@ def prehead_backward(grad_out, feat, stats, weight, bias, n_groups, gamma, beta,
     if C == 0 and (want[5] or "grad_emb" in out):
         raise ValueError("prehead_backward: the embedding's gradient needs C > 0")
     shapes = (tuple(feat.shape), (n_out, n_in), (n_out,), (n_out,), (n_out,), tuple(feat.shape[2:]) + (C,))
-    bufs = []
-    for name, shape, w in zip(OUTS, shapes, want):
-        if name in out:
-            bufs.append(ops._out("prehead_backward: " + name, out[name], shape))
-        else:
-            bufs.append(torch.empty(shape, dtype=torch.float32, device=feat.device) if w else None)
+    bufs = _wanted("prehead_backward", OUTS, shapes, want, out, feat)
     L = _lib.lib()
     ws = ops._ws(L.aoc_prehead_grad_workspace_bytes(O, n_in, n_out, n_groups, hw), feat.device)
     _lib.check(L.aoc_prehead_grad(ops._p(grad_out), ops._p(feat), ops._p(stats), ops._p(weight), ops._p(bi), ops._p(g), ops._p(b), O, n_in, n_out, n_groups,
                                   hw, C, *(ops._p(t) for t in bufs), ops._p(ws), ws.numel(), ops._stream()), "aoc_prehead_grad")
-    return tuple(bufs)
+    return bufs
 
 
 # ------------------------------------------------------------------------------------------ autograd
-def _det(t):
-    return ops._f32c(t.detach()) if t is not None else None
-
-
 class _PreHead(torch.autograd.Function):
     """feat [O, n_in, h, w], weight, bias, gamma, beta, emb [h, w, C] or None -> [O, C + n_out, h, w] by aoc_prehead; saves feat, the
     statistics and the parameters -- not the output."""

@@ -21,25 +21,18 @@ the head x, the two rows [N, C + 1] and arg.  Without a wanted gradient every fu
 own ``ops`` calls; with one, the forward calls the same C entry points (``aoc_logit_head_argmin`` repeats ``aoc_logit_head``'s sums term by
 term), so the output bits are the mirror's.  ``ctx.needs_input_grad`` selects which optional outputs the kernels are asked for.  All backwards
 are ``once_differentiable``; every sum runs in a fixed order without float atomics.  The ctypes wrappers of the new entry points live here,
-not in ``ops`` (whose public names are a tested table); they keep ``ops``' tensor contract: inputs converted by ``_f32c`` / ``_i32c`` into
-names that live until the call, caller outputs checked by ``_out``, addresses only through ``_p``.
+not in ``ops`` (whose public names are a tested table); they keep ``ops``' tensor contract through its helpers: inputs converted by
+``_f32c`` / ``_opt`` / ``_i32c`` into names that live until the call, caller outputs checked by ``_out`` (the named optional ones chosen by
+``_wanted``), addresses only through ``_p``.
 """
 import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib, decoder_tail, decoder_train, gates_train, gct, ops
-from .matching_train import _wants_grad
+from .ops import _det, _new, _opt, _wanted, _wants_grad
 
 
 # ------------------------------------------------------------------------------------------ the C ABI
-def _opt(t):
-    return ops._f32c(t) if t is not None else None
-
-
-def _new(like, *shape, dtype=torch.float32):
-    return torch.empty(*shape, dtype=dtype, device=like.device)
-
-
 def _stage_shapes(what, grad_out, x, low):
     if grad_out.dim() != 4 or x is None or x.dim() != 4 or grad_out.numel() == 0 or x.numel() == 0:
         raise ValueError(f"{what}: grad_out [N, Ce + Cr, H, W] and x [N, Ce, h, w] are needed (x for its shape at least)")
@@ -153,22 +146,15 @@ def logit_head_backward(grad_pred, arg, x, wb_fg, wb_bg, want=(True, True, True)
     grad_pred, x, wb_fg, wb_bg = ops._f32c(grad_pred), ops._f32c(x), ops._f32c(wb_fg), _opt(wb_bg)
     arg = ops._i32c(arg) if arg is not None else None
     out = dict(out or {})
-    if set(out) - set(_HEAD_OUTS):
-        raise ValueError(f"logit_head_backward: unknown outputs {sorted(set(out) - set(_HEAD_OUTS))}")
     ops._need_gpu(grad_pred, arg, x, wb_fg, wb_bg, *out.values())
     N, C, H, W = _head_shapes("logit_head_backward", x, wb_fg, wb_bg)
     if grad_pred.numel() != N * H * W or (N > 1 and (arg is None or arg.numel() != H * W)):
         raise ValueError(f"logit_head_backward: grad_pred must hold {N * H * W} elements and arg {H * W}")
-    bufs = []
-    for name, shape, w_ in zip(_HEAD_OUTS, (tuple(x.shape), (N, C + 1), (N, C + 1)), want):
-        if name in out:
-            bufs.append(ops._out("logit_head_backward: " + name, out[name], shape))
-        else:
-            bufs.append(_new(x, *shape) if w_ else None)
+    bufs = _wanted("logit_head_backward", _HEAD_OUTS, (tuple(x.shape), (N, C + 1), (N, C + 1)), want, out, x)
     grad_x, grad_fg, grad_bg = bufs
     _lib.check(_lib.lib().aoc_logit_head_grad(ops._p(grad_pred), ops._p(arg), ops._p(x), ops._p(wb_fg), ops._p(wb_bg), C + 1, N, C, H * W, ops._p(grad_x),
                                               ops._p(grad_fg), ops._p(grad_bg), ops._stream()), "aoc_logit_head_grad")
-    return tuple(bufs)
+    return bufs
 
 
 def background_merge_forward(fg_logit, bg_logit, pred=None, arg=None):
@@ -208,10 +194,6 @@ def background_merge_backward(grad_pred, arg, grad_fg=None, grad_bg=None, want=(
 
 
 # ------------------------------------------------------------------------------------------ autograd
-def _det(t):
-    return ops._f32c(t.detach()) if t is not None else None
-
-
 class _ShortcutStage(torch.autograd.Function):
     """x [N, Ce, h, w], low [N, Cr, H, W], head [N, D], weight [Ce + Cr, D + Ce + Cr], bias or None -> IA10(cat([bicubic(x), low], 1), cat([head,
     px1_delta], 1)) by aoc_shortcut_stage_enqueue; saves x, low, the head, the weight and the plane means and gain the call emits."""

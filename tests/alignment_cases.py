@@ -114,15 +114,15 @@ for _e in ("aoc_dense_match_min_split", "aoc_dense_match_min_split_cached"):
     WHY[(_e, "pool_rec")] = "dense_split.hip:165-166 (uint4 load in split_plan_kernel), :426 (LDS-direct global_load_lds_dwordx4, :239); opaque records"
     WHY[(_e, "workspace")] = "dense_split.hip:414 (LDS-direct 16-byte loads of the tile row lists the plan leaves in the workspace)"
 for _e in ("aoc_local_window_match", "aoc_local_window_match_ex"):
-    WHY[(_e, "query")] = "local_match.hip:230 via :260 (register-operand kernel, C = 100 / 128: float4 pieces of the query row)"
-    WHY[(_e, "prev")] = "local_match.hip:92 (LDS-image kernel) and :230 via :286 (register-operand kernel): float4 loads of the candidate rows"
+    WHY[(_e, "query")] = "local_match.hip:219 via :249 (register-operand kernel, C = 100 / 128: float4 pieces of the query row)"
+    WHY[(_e, "prev")] = "local_match.hip:81 (LDS-image kernel) and :219 via :275 (register-operand kernel): float4 loads of the candidate rows"
 WHY[("aoc_local_window_match_pair", "query")] = WHY[("aoc_local_window_match", "query")]
 WHY[("aoc_local_window_match_pair", "prev_a")] = WHY[("aoc_local_window_match", "prev")]
 WHY[("aoc_local_window_match_pair", "prev_b")] = WHY[("aoc_local_window_match", "prev")]
-WHY[("aoc_local_window_match_argmin", "query")] = "local_grad.hip:97 via :124 (float4 pieces of the query row, C = 100 / 128)"
-WHY[("aoc_local_window_match_argmin", "prev")] = "local_grad.hip:97 via :146 and :238 (float4 loads of the candidate rows in both kernels)"
-WHY[("aoc_atrous_subsample", "in")] = "local_match.hip:446 (float4 moves when X % 4 == 0)"
-WHY[("aoc_atrous_subsample", "out")] = "local_match.hip:446 (float4 moves when X % 4 == 0)"
+WHY[("aoc_local_window_match_argmin", "query")] = "local_grad.hip:92 via :119 (float4 pieces of the query row, C = 100 / 128)"
+WHY[("aoc_local_window_match_argmin", "prev")] = "local_grad.hip:92 via :141 and :229 (float4 loads of the candidate rows in both kernels)"
+WHY[("aoc_atrous_subsample", "in")] = "local_match.hip:435 (float4 moves when X % 4 == 0)"
+WHY[("aoc_atrous_subsample", "out")] = "local_match.hip:435 (float4 moves when X % 4 == 0)"
 WHY[("aoc_frame_enqueue", "workspace")] = "frame.hip:128 (frame_carve: the records, the dense and correlation workspaces and the half-resolution maps handed to the entries below)"
 WHY[("aoc_frame_desc", "ref_emb")] = "frame.hip:184, 195 (aoc_split_rows x, aoc_dense_match_min_split_cached pool when match_hw == 0)"
 WHY[("aoc_frame_desc", "match_emb")] = "frame.hip:184, 195 (aoc_split_rows x, aoc_dense_match_min_split_cached pool when match_hw > 0)"
