@@ -1539,6 +1539,68 @@ int aoc_clip_sgd_step(aoc_mt_tensor *table, aoc_mt_tensor *table_host, int n_ten
                       const float *lr_dev, float momentum, float dampening, int nesterov, int zero_grad, void *workspace, size_t workspace_bytes,
                       aoc_stream_t stream);
 
+/*
+ * The hand-over between two frames of a training step (csrc/train_step.hip; aoc_amd.train_step): what train_manager_mm.py:241-284 does with the
+ * model's prediction,
+ *   train_manager_mm.py:277       iou = pytorch_iou(all_pred.unsqueeze(1), curr_labels, obj_nums)        (utils/metric.py:3-34)
+ *   train_manager_mm.py:281-282   running_losses[idx].update(loss.item() * seq_len); running_ious[idx].update(iou.item())   (utils/meters.py)
+ *   train_manager_mm.py:258-259   prev_labels = all_pred.unsqueeze(1), shrunk by aocnet.py:134-135 interpolate(mode='nearest').int()
+ * as one call per frame for the whole batch: two launches, nothing allocated, nothing synchronised, every argument validated before the
+ * first launch (a rejected call enqueues and writes nothing).
+ *
+ * pred, gt [bs, H, W], each with its own dtype code (AOC_LABEL_I32 / _I64 / _F32: float32 maps of integers, as the loader's masks are).  A
+ * value v names object o iff v == o as numbers: 255, negatives, ids above the sample's obj_num and non-integers match nothing.
+ * obj_num_host [bs]: a HOST array, each 0 .. AOC_MAX_OBJECTS (negative: AOC_ERR_INVALID_ARG, larger: AOC_ERR_UNSUPPORTED).
+ * mode AOC_IOU_PER_COLUMN is the reference AS IT IS CALLED: with [bs, 1, H, W] inputs metric.py's `== obj_ids` broadcasts to [1, n, H, W]
+ * and .sum((1, 2)) runs over the objects and the rows, so a sample's value is the mean over the W columns x of (I[x] + eps) / (U[x] + eps),
+ *   I[x] = #rows with pred == gt and the id in 1 .. n            U[x] = sum over the rows of [pred in 1..n] + [gt in 1..n] - [both and equal]
+ * mode AOC_IOU_PER_OBJECT is the function as documented ([bs, h, w] inputs): the mean over the objects o = 1 .. n of (I[o] + eps) / (U[o] + eps),
+ *   I[o] = #pixels with pred == gt == o      U[o] = #pred[o] + #gt[o] - I[o]
+ * Arithmetic, so that a float32 restatement gives the same bits: the counts are integers (how they are gathered changes nothing); a ratio is
+ * ((float)I + eps) / ((float)U + eps), one rounding per operation; a sample's mean over its n terms (W columns or obj_num objects): thread
+ * t of 256 adds the terms t, t + 256, ... ascending from 0.0f, then the xor butterfly over the wave (32 .. 1) and the four wave sums as
+ * (w0 + w1) + (w2 + w3), then the division by (float)n; the batch mean: the samples with obj_num > 0 in ascending order from 0.0f, divided by
+ * their number, 1.0f when there is none (metric.py's `continue` and its torch.ones).  H * W <= 2^24 and bs * H * W < 2^31, beyond either
+ * AOC_ERR_UNSUPPORTED (without reading a buffer).  No float atomics, no atomics on global memory: equal inputs give equal bits.
+ *
+ * Outputs, each optional (NULL: skipped), at least one; each has alone the bits it has with the others:
+ *   iou             one float
+ *   iou_per_sample  [bs]; 1.0f where obj_num == 0 (such samples are left out of the batch mean)
+ *   counts          mode 0: [bs, W, 2] uint32 = I[x], U[x];   mode 1: [bs, AOC_MAX_OBJECTS, 3] uint32 = I[o], #pred[o], #gt[o] (0 behind obj_num)
+ *   prev_small      [bs, small_h, small_w] int32: pred through torch's nearest rule, source row min((int)floorf((float)y * ((float)H /
+ *                   (float)small_h)), H - 1) and the column likewise; an int64 value is narrowed, a float one goes through (int)v.  Needs
+ *                   small_h, small_w >= 1; with prev_small alone gt, obj_num_host and the workspace may be NULL (one launch)
+ *   meter           one record updated with iou and n = 1 as aoc_meters_update does (8-byte aligned)
+ * All other pointers are class 4 (an int64 map too: sample 1 of an odd H * W starts off every wider grid) and no bit depends on where one
+ * sits.  The workspace (class 4, aoc_frame_handover_workspace_bytes(bs, H, W), else AOC_ERR_WORKSPACE) may hold anything on entry.
+ *
+ * aoc_meter follows utils/meters.py AverageMeter.update(val, n): with x = (double)value[0] * scale (the reference's `loss.item() * seq_len`
+ * in Python's double arithmetic), val = (float)x, sum += x * n, count += n, avg = (float)(sum / count); a zeroed record is a fresh meter.
+ * aoc_meters_update: one launch for k <= AOC_METERS_PER_CALL updates (more: AOC_ERR_UNSUPPORTED) of distinct meters index_host[j] < n_meters
+ * of the device array `meters`, each from its own device float word values_host[j] with scale_host[j] and n_host[j] >= 1 (all four HOST
+ * arrays; a repeated index, a NULL word or n < 1: AOC_ERR_INVALID_ARG).  aoc_meters_reset: one launch zeroes the meters whose bit is set in
+ * `mask` (n_meters <= 64; a bit at or above n_meters: AOC_ERR_INVALID_ARG).  Neither synchronises.
+ */
+#define AOC_LABEL_I32 0
+#define AOC_LABEL_I64 1
+#define AOC_LABEL_F32 2
+#define AOC_IOU_PER_COLUMN 0
+#define AOC_IOU_PER_OBJECT 1
+#define AOC_METERS_PER_CALL 8
+typedef struct aoc_meter {
+    float val;
+    float avg;
+    double sum;
+    int64_t count;
+} aoc_meter;
+size_t aoc_frame_handover_workspace_bytes(int bs, int H, int W);
+int aoc_frame_handover(const void *pred, int pred_dtype, const void *gt, int gt_dtype, int bs, int H, int W, const int32_t *obj_num_host,
+                       float epsilon, int mode, int small_h, int small_w, float *iou, float *iou_per_sample, uint32_t *counts, int32_t *prev_small,
+                       aoc_meter *meter, void *workspace, size_t workspace_bytes, aoc_stream_t stream);
+int aoc_meters_update(aoc_meter *meters, int n_meters, const int32_t *index_host, const float *const *values_host, const double *scale_host,
+                      const int64_t *n_host, int k, aoc_stream_t stream);
+int aoc_meters_reset(aoc_meter *meters, int n_meters, uint64_t mask, aoc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

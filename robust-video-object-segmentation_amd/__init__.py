@@ -47,7 +47,8 @@ from . import aspp_train  # noqa: F401,E402
 from . import loss_train  # noqa: F401,E402
 from . import prehead_train  # noqa: F401,E402
 from . import optim_train  # noqa: F401,E402
+from . import train_step  # noqa: F401,E402
 
 __all__ = ["synthetic", "ops", "matching", "attention", "conditioning_layer", "hotpath", "sharding", "eval_loop", "gct", "eval_runner", "decoder_tail",
            "decoder_memory", "aspp", "matching_train", "local_train", "cluster_train", "frontend_train", "gates_train", "decoder_train",
-           "tail_train", "aspp_train", "loss_train", "prehead_train", "optim_train"]
+           "tail_train", "aspp_train", "loss_train", "prehead_train", "optim_train", "train_step"]

@@ -185,6 +185,10 @@ SIGNATURES = {
     "aoc_sgd_step": (_i, [_vp, _vp, _i, _i64, _vp, _f, _vp, _f, _f, _i, _i, _vp]),
     "aoc_clip_sgd_step_workspace_bytes": (_sz, [_i64]),
     "aoc_clip_sgd_step": (_i, [_vp, _vp, _i, _i64, _f, _vp, _f, _vp, _f, _f, _i, _i, _vp, _sz, _vp]),
+    "aoc_frame_handover_workspace_bytes": (_sz, [_i, _i, _i]),
+    "aoc_frame_handover": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "aoc_meters_update": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "aoc_meters_reset": (_i, [_vp, _i, ctypes.c_uint64, _vp]),
 }
 
 STATUS = {0: "AOC_OK", -1: "AOC_ERR_INVALID_ARG", -2: "AOC_ERR_WORKSPACE", -3: "AOC_ERR_LAUNCH", -4: "AOC_ERR_UNSUPPORTED"}
