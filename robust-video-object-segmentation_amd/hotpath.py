@@ -65,14 +65,42 @@ def channel_slices(cfg):
 class ClusterProxiesAhead:
     """Adaptive proxies of ONE frame computed ahead of time on a side stream (launch_cluster_proxies): the k-means
     chain only depends on the reference pool, its labels and the initial rows -- not on the frame before -- so while the
-    pool is unchanged (4 of 5 frames with MEM_EVERY = 5) the chain of frame t+1 can run under frame t's other work."""
+    pool is unchanged (4 of 5 frames with MEM_EVERY = 5) the chain of frame t+1 can run under frame t's other work.
+
+    Slots, and what they hold in each of the three sources -- the chain (launch_cluster_proxies[_batch]), prepare_without_clustering, and the
+    bank (IncrementalProxyBank.handle):
+      R             pool frames the handle was made for
+      prep          ops.LabelPrep of the pool's labels
+      table, sqn    the frame's proxy table [adaptive rows + O, C] and its squared norms; the k = 1 rows (the last O) are left to the frame
+                    call.  Chain: allocated on the side stream, adaptive rows written by the chain.  prepare_without_clustering: zeros / +inf.
+                    Bank: the bank's OWN tensors (shared by every handle).
+      prep_event    recorded when `prep` is complete.  Chain: on the side stream, in front of the chain.  Otherwise: on the caller's stream.
+      done_event    recorded when the adaptive rows are complete.  Chain: on the side stream, after the chain (one event for every frame of a
+                    batch).  prepare_without_clustering: the prep_event itself.  Bank: the event of its last append (None before the first).
+      aux           chain: dict(prep, centroids, proxies, proxy_sqnorm, seg_k, seg_offsets, labels (None in a batch), chain = the
+                    ops.cluster_chain result, which keeps the inputs alive).  Otherwise None.
+      cluster_sets  bank: (set_begin, set_size, adaptive rows) of its own table layout.  Otherwise None."""
     __slots__ = ("prep", "table", "sqn", "prep_event", "done_event", "aux", "R", "cluster_sets")
+
+    def __init__(self, *, R, prep, table, sqn, prep_event, done_event, aux=None, cluster_sets=None):
+        self.R, self.prep, self.table, self.sqn = R, prep, table, sqn
+        self.prep_event, self.done_event, self.aux, self.cluster_sets = prep_event, done_event, aux, cluster_sets
+
+    def read_on(self, stream):
+        """`stream` (the caller's) now reads the table, its norms and the prep lists: they were allocated under another stream, and the caching
+        allocator must not hand their blocks out again while `stream` still reads them."""
+        for t in (self.table, self.sqn, *self.prep.tensors()):
+            t.record_stream(stream)
+
+
+def adaptive_proxy_rows(cfg, n_obj):
+    """Rows of the adaptive part of one frame's proxy table: levels x objects x (centroid | centroid_avg) x kmax."""
+    return ops._adaptive_rows(cfg.cluster_levels, n_obj)
 
 
 def proxy_table_rows(cfg, n_obj):
-    """Rows of one frame's proxy table: levels x objects x (centroid | centroid_avg) x kmax adaptive proxies, then the n_obj k = 1 proxies."""
-    levels = cfg.cluster_levels
-    return len(levels) * n_obj * 2 * max(levels) + n_obj
+    """Rows of one frame's proxy table: the adaptive proxies, then the n_obj k = 1 proxies."""
+    return adaptive_proxy_rows(cfg, n_obj) + n_obj
 
 
 def launch_cluster_proxies_batch(cfg, ref_emb, ref_labels, init_rows_list, side_stream=None, wait_event=None, prep=None):
@@ -97,11 +125,10 @@ def launch_cluster_proxies_batch(cfg, ref_emb, ref_labels, init_rows_list, side_
     hw = h * w
     levels = cfg.cluster_levels
     L, kmax = len(levels), max(levels)
-    n_ad = L * O * 2 * kmax
+    rows = proxy_table_rows(cfg, O)
     dev = ref_emb.device
     main = torch.cuda.current_stream()
     side = main if side_stream is None else side_stream
-    outs = []
     with torch.cuda.stream(side):
         if side is not main:
             if wait_event is not None:
@@ -114,13 +141,13 @@ def launch_cluster_proxies_batch(cfg, ref_emb, ref_labels, init_rows_list, side_
                 t.record_stream(side)
         # the per-frame proxy tables are allocated BEFORE the chain: the caller's stream writes their k = 1 rows as soon as the label
         # prep is done, so they must not share a block with any temporary of the chain that is still running on this stream
-        tables = [torch.empty(n_ad + O, C, dtype=torch.float32, device=dev) for _ in range(F)]
-        sqns = [torch.empty(n_ad + O, dtype=torch.float32, device=dev) for _ in range(F)]
+        tables = [torch.empty(rows, C, dtype=torch.float32, device=dev) for _ in range(F)]
+        sqns = [torch.empty(rows, dtype=torch.float32, device=dev) for _ in range(F)]
         pool = ref_emb.reshape(R * hw, C)
         if prep is None:
             prep = ops.label_prep(ref_labels.reshape(R * hw, O))
         elif side is not main:
-            for t in (prep.right_bits, prep.wrong_bits, prep.fg_rows, prep.obj_rows, prep.counts, prep.obj_offsets):
+            for t in prep.tensors():
                 t.record_stream(side)
         prep_event = torch.cuda.Event()
         prep_event.record(side)
@@ -128,40 +155,34 @@ def launch_cluster_proxies_batch(cfg, ref_emb, ref_labels, init_rows_list, side_
         # ONE C call (aoc_cluster_chain_enqueue): replicated lists with the sticky K, 20 Lloyd iterations, proxy construction, and every frame's
         # proxies scattered into its own table -- what used to be three C calls, a dozen allocations and 2 F table copies (same results)
         ch = ops.cluster_chain(pool, prep, levels, init.reshape(F * L * O, kmax), tables, sqns, KMEANS_ITERS)
-        for f in range(F):
-            out = ClusterProxiesAhead()
-            out.R = R
-            out.cluster_sets = None
-            out.prep, out.prep_event = prep, prep_event
-            out.table, out.sqn = tables[f], sqns[f]
-            sl = slice(f * L * O, (f + 1) * L * O)
-            out.aux = dict(prep=prep, centroids=ch["centroids"][sl], proxies=ch["proxies"][sl], proxy_sqnorm=ch["proxy_sqnorm"][sl], seg_k=ch["seg_k"][sl],
-                           seg_offsets=ch["seg_offsets"], labels=ch["labels"] if F == 1 else None, chain=ch)
-            outs.append(out)
         done = torch.cuda.Event()
         done.record(side)
-        for out in outs:
-            out.done_event = done
+    outs = []
+    for f in range(F):
+        sl = slice(f * L * O, (f + 1) * L * O)
+        aux = dict(prep=prep, centroids=ch["centroids"][sl], proxies=ch["proxies"][sl], proxy_sqnorm=ch["proxy_sqnorm"][sl], seg_k=ch["seg_k"][sl],
+                   seg_offsets=ch["seg_offsets"], labels=ch["labels"] if F == 1 else None, chain=ch)
+        outs.append(ClusterProxiesAhead(R=R, prep=prep, table=tables[f], sqn=sqns[f], prep_event=prep_event, done_event=done, aux=aux))
     return outs
+
+
+def _prep_on_this_stream(labels_flat):
+    """(label prep of the pool's labels, the event that marks it complete) on the current stream."""
+    prep, event = ops.label_prep(labels_flat), torch.cuda.Event()
+    event.record()
+    return prep, event
 
 
 def prepare_without_clustering(cfg, ref_emb, ref_labels):
     """cfg.MODEL_FLOAT16_MATCHING: the reference's cluster channels are the constant 1 (scipy rejects float16 data), so a frame needs no k-means
     chain -- only the label prep of the pool the matchings see and a proxy table for its k = 1 rows.  Returns the ClusterProxiesAhead that
     FrameRunner / proto_mask_features(cluster_ahead=...) take."""
-    R, h, w, C = ref_emb.shape
-    O = ref_labels.shape[-1]
-    levels = cfg.cluster_levels
-    n_ad = len(levels) * O * 2 * max(levels)
-    out = ClusterProxiesAhead()
-    out.R, out.cluster_sets, out.aux = R, None, None
-    out.prep = ops.label_prep(ref_labels.reshape(-1, O))
-    out.prep_event = torch.cuda.Event()
-    out.prep_event.record()
-    out.table = torch.zeros(n_ad + O, C, dtype=torch.float32, device=ref_emb.device)
-    out.sqn = torch.full((n_ad + O,), float("inf"), dtype=torch.float32, device=ref_emb.device)
-    out.done_event = out.prep_event
-    return out
+    R, C, O = ref_emb.shape[0], ref_emb.shape[-1], ref_labels.shape[-1]
+    rows = proxy_table_rows(cfg, O)
+    prep, event = _prep_on_this_stream(ref_labels.reshape(-1, O))
+    return ClusterProxiesAhead(R=R, prep=prep, prep_event=event, done_event=event,
+                               table=torch.zeros(rows, C, dtype=torch.float32, device=ref_emb.device),
+                               sqn=torch.full((rows,), float("inf"), dtype=torch.float32, device=ref_emb.device))
 
 
 def launch_cluster_proxies(cfg, ref_emb, ref_labels, init_rows_dev, side_stream=None, wait_event=None, prep=None):
@@ -217,18 +238,10 @@ class IncrementalProxyBank:
         R <= the number of frames in the bank)."""
         R = ref_labels.shape[0]
         assert 1 <= R <= self.R, "the bank holds fewer pool frames"
-        out = ClusterProxiesAhead()
-        out.R = R
-        out.prep = ops.label_prep(ref_labels.reshape(-1, self.O))
-        out.prep_event = torch.cuda.Event()
-        out.prep_event.record()
-        out.done_event = self.done_event
-        out.table, out.sqn = self.table, self.sqn
-        out.aux = None
+        prep, event = _prep_on_this_stream(ref_labels.reshape(-1, self.O))
         # set (object, centroid | centroid_avg) = the K proxies of each of the R pool frames: contiguous rows of the table
-        out.cluster_sets = ([(o * 2 + f) * self.cap * self.K for o in range(self.O) for f in range(2)], [R * self.K] * (2 * self.O),
-                            self.O * 2 * self.cap * self.K)
-        return out
+        sets = ([(o * 2 + f) * self.cap * self.K for o in range(self.O) for f in range(2)], [R * self.K] * (2 * self.O), self.O * 2 * self.cap * self.K)
+        return ClusterProxiesAhead(R=R, prep=prep, table=self.table, sqn=self.sqn, prep_event=event, done_event=self.done_event, cluster_sets=sets)
 
 
 class PendingCorrelation:
@@ -263,6 +276,237 @@ def launch_correlations(pending, stream=None, precision="split"):
         done = torch.cuda.Event()
         done.record(stream)
     return done
+
+
+class _Frame:
+    """What the stages of proto_mask_features read of one frame, named once: the configuration, the shapes (R pool frames, h x w map, hw pixels,
+    C channels, O objects, nl local radii), the result `feat` [O, n_ch, h, w] with its channel map `ch` and object stride, the levels and the
+    adaptive rows `n_ad` of the proxy table, the float16 flag, the resolved precision ("f16" / "split" / "fp32"), the bias vector, and the rows of the pool the dense and
+    cluster matchings see, of its labels and of the query."""
+    __slots__ = ("cfg", "R", "h", "w", "hw", "C", "O", "dev", "nl", "ch", "obj_stride", "levels", "n_ad", "f16", "precision", "bias", "feat", "pool", "labels_flat",
+                 "query_flat")
+
+    def __init__(self, cfg, ref_emb, ref_labels, m_emb, m_lab, cur_emb, dis_bias, dense_precision, cluster_ahead):
+        self.cfg = cfg
+        self.R, self.h, self.w, self.C = ref_emb.shape
+        self.O, self.hw, self.dev = ref_labels.shape[-1], self.h * self.w, cur_emb.device
+        self.nl, self.ch = len(cfg.MODEL_MULTI_LOCAL_DISTANCE), channel_slices(cfg)
+        self.bias = _bias_vec(dis_bias, self.O, self.dev)
+        self.feat = torch.empty(self.O, cfg.proto_channels, self.h, self.w, dtype=torch.float32, device=self.dev)
+        self.obj_stride, self.levels, self.f16 = cfg.proto_channels * self.hw, cfg.cluster_levels, bool(cfg.MODEL_FLOAT16_MATCHING)
+        self.precision = "f16" if self.f16 else (dense_precision or ops.DENSE_PRECISION)      # "f16": AEM:801-803 on float16 tensors
+        # (IncrementalProxyBank: its own table layout)
+        bank = cluster_ahead is not None and cluster_ahead.cluster_sets is not None
+        self.n_ad = cluster_ahead.cluster_sets[2] if bank else adaptive_proxy_rows(cfg, self.O)
+        self.pool = m_emb.reshape(-1, self.C)                            # what the dense and cluster matchings see
+        self.labels_flat = m_lab.reshape(-1, self.O)
+        self.query_flat = cur_emb.reshape(self.hw, self.C)
+
+
+def _proxies_ahead(fr, main, ahead):
+    """Stage 1, with a ClusterProxiesAhead (the caller's, or the chain launched from cluster_state): the adaptive proxies are on their way on
+    another stream; the frame's stream waits for the label prep only -> (table, sqn, prep, aux of the chain)."""
+    assert ahead.R == fr.R, "cluster_ahead was launched for another pool size"
+    main.wait_event(ahead.prep_event)
+    ahead.read_on(main)
+    return ahead.table, ahead.sqn, ahead.prep, ahead.aux
+
+
+def _proxies_inline(fr, init_rows, rng):
+    """Stage 1 without one: the k-means chain on this stream (with a host read-back of the row counts), copied into a table allocated here
+    -> (table, sqn, prep, cluster_proxies' result)."""
+    n_ad = fr.n_ad
+    table = torch.empty(n_ad + fr.O, fr.C, dtype=torch.float32, device=fr.dev)
+    sqn = torch.empty(n_ad + fr.O, dtype=torch.float32, device=fr.dev)
+    # (float16 matching: no clustering at all -- scipy rejects float16 data and the reference's cluster channels are the constant 1)
+    cp = cluster_proxies(fr.pool, fr.labels_flat, fr.levels if fr.cfg.CLUSTER_LEVELS else fr.levels[0], init_rows, rng) if not fr.f16 else None
+    prep = cp["prep"] if cp is not None else ops.label_prep(fr.labels_flat)
+    if cp is not None:
+        table[:n_ad].copy_(cp["proxies"].reshape(-1, fr.C))
+        sqn[:n_ad].copy_(cp["proxy_sqnorm"].reshape(-1))
+    else:
+        sqn[:n_ad].fill_(float("inf"))       # nothing labelled -> every cluster feature is 1
+    return table, sqn, prep, cp
+
+
+def _pooled_heads(fr, ref_emb, ref_labels, prev_emb, prev_labels, table, sqn, dense_state):
+    """Stage 2: the pooled heads (ATT:155-189) of the pool -- into the k = 1 rows of the proxy table, at once or as copies still to be made --
+    and of the previous frame -> (ref_pos, ref_neg, prev_pos, prev_neg, k1_copies)."""
+    R, hw, C, O, n_ad, eps = fr.R, fr.hw, fr.C, fr.O, fr.n_ad, fr.cfg.MODEL_EPSILON
+    cached = dense_state.get("ref_pool") if dense_state is not None else None
+    k1_copies = []
+    if cached is not None and cached[0] == R:
+        # the pooled reference heads are a function of the pool alone (ATT:155-170): unchanged since the last frame
+        _, ref_pos, ref_neg, ref_sq = cached
+        k1_copies = [(ref_pos, table[n_ad:]), (ref_sq, sqn[n_ad:])]       # into the k = 1 rows of this frame's proxy table (by the local-prep launch)
+    else:
+        ref_pos, ref_neg = ops.masked_mean_pool(ref_emb.reshape(R, hw, C), ref_labels.reshape(R, hw, O), eps, pixel_major=True,
+                                                out_pos=table[n_ad:], out_pos_sqnorm=sqn[n_ad:])
+        if dense_state is not None:
+            dense_state["ref_pool"] = (R, ref_pos.clone(), ref_neg, sqn[n_ad:].clone())
+    prev_pos, prev_neg = ops.masked_mean_pool(prev_emb.reshape(1, hw, C), prev_labels.reshape(1, hw, O), eps, pixel_major=True)
+    return ref_pos, ref_neg, prev_pos, prev_neg, k1_copies
+
+
+def _split_records(fr, prep, dense_state):
+    """Stage 3: the fp16 split records the "split" precision streams -- the pool's, kept in dense_state and extended by the frames that joined
+    since the last call; the query's -> (pool_split, query_split), None where the records do not exist."""
+    R, C, pool = fr.R, fr.C, fr.pool
+    split = fr.precision == "split"
+    pool_split = None
+    if dense_state is not None and split and ops.split_record_bytes(C):
+        pool_split = dense_state.get("pool_split")
+        frames_done = dense_state.get("frames", 0)
+        mhw = pool.shape[0] // R
+        if pool_split is None or pool_split.records.shape[0] < R * mhw:
+            cap = max(R, dense_state.get("capacity_frames", R)) * mhw
+            pool_split = ops.SplitRows()
+            pool_split.records = torch.empty(cap, ops.split_record_bytes(C), dtype=torch.uint8, device=fr.dev)
+            pool_split.sqnorm = torch.empty(cap, dtype=torch.float32, device=fr.dev)
+            pool_split.overflow = torch.zeros(1, dtype=torch.int32, device=fr.dev)
+            pool_split.n = cap
+            frames_done = 0
+        if frames_done < R:
+            ops.split_rows(pool[frames_done * mhw:R * mhw], out=pool_split, row0=frames_done * mhw)
+        # records of pool frames [0, max(frames_done, R)) are valid; a caller that restarts the pool (new sequence) resets "frames" to 0
+        dense_state["pool_split"], dense_state["frames"] = pool_split, max(frames_done, R)
+    # the query's split records, ONCE per frame and tile-major: the dense kernel and the correlation kernel both stream them in their MFMA
+    # operand layout (the correlation kernel reads the fp32 rows only on its exact-fp32 take-over)
+    query_split = None
+    if split and ops.split_record_bytes(C) and C == 100 and prep.n_obj <= 16:
+        query_split = ops.split_rows(fr.query_flat, overflow=pool_split.overflow if pool_split is not None else None, tiled=True)
+    return pool_split, query_split
+
+
+def _dense_matching(fr, main, prep, query_split, pool_split, dense_stream):
+    """Stage 4: dense pixel-level matching, AEM:688-817 -> channel 0; on dense_stream when given -> the event to join on (or None)."""
+    if dense_stream is None:
+        ops.dense_match(fr.query_flat, fr.pool, prep, fr.bias, fr.feat, 1, fr.obj_stride, True, precision=fr.precision, query_split=query_split,
+                        pool_split=pool_split)
+        return None
+    dense_stream.wait_stream(main)
+    with torch.cuda.stream(dense_stream):
+        ops.dense_match(fr.query_flat, fr.pool, prep, fr.bias, fr.feat, 1, fr.obj_stride, True, precision=fr.precision, query_split=query_split,
+                        pool_split=pool_split)
+        dense_done = torch.cuda.Event()
+        dense_done.record(dense_stream)
+    fr.feat.record_stream(dense_stream)
+    if query_split is not None:
+        query_split.records.record_stream(dense_stream)
+        query_split.sqnorm.record_stream(dense_stream)
+    return dense_done
+
+
+def _local_matching(fr, cur_emb, prev_emb, prev_flat_labels, prev_pos, k1_copies):
+    """Stage 5: local matching against the previous frame and against its per-pixel proxy map (aocnet.py:255,325-337) -> the k1_copies that no
+    launch of this stage took along."""
+    cfg, h, w, hw, C, O, nl, ch, f16 = fr.cfg, fr.h, fr.w, fr.hw, fr.C, fr.O, fr.nl, fr.ch, fr.f16
+    base = fr.feat.view(-1)
+    radii = list(cfg.MODEL_MULTI_LOCAL_DISTANCE)
+    lrate = max(1, int(cfg.TEST_LOCAL_ATROUS_RATE))
+    if cfg.MODEL_LOCAL_DOWNSAMPLE and not f16 and lrate == 1:
+        # one launch for the three bilinear down-samples, the (never materialised) proxy map and the label bits; one for both matchings;
+        # one for both up-samples into their channel ranges
+        H2, W2 = int(h / 2) + 1, int(w / 2) + 1
+        q2, p2, pm2, bits2 = ops.local_prep(cur_emb, prev_emb, prev_flat_labels, prev_pos, H2, W2, copies=k1_copies)
+        lf = ops.local_window_match_pair(q2, p2, pm2, bits2, radii, fr.bias, O, True)          # [2, O, nl, H2, W2]
+        ops.resize_bilinear_planes_grouped(lf.view(2 * O * nl, H2, W2), h, w, base[ch["local"] * hw:], nl, O, (ch["local_proxy"] - ch["local"]) * hw,
+                                           fr.obj_stride, hw, 1)
+        return []
+    # matching.local_matching / local_matching_proxy step by step (AEM:968-1060): full resolution (MODEL_LOCAL_DOWNSAMPLE off), the float16
+    # arithmetic (down-samples of float16 tensors), the atrous window stride
+    right_prev, _ = ops.label_bits(prev_flat_labels, want_wrong=False)
+    proxy_map = ops.label_mix(prev_flat_labels, prev_pos).view(h, w, C)                # aocnet.py:325
+    Hm, Wm, qm = h, w, cur_emb
+    if cfg.MODEL_LOCAL_DOWNSAMPLE:
+        Hm, Wm = int(h / 2) + 1, int(w / 2) + 1
+        qm = ops.resize_bilinear_hwc(cur_emb, Hm, Wm, float16=f16)
+        right_prev = ops.resize_nearest_bits(right_prev, h, w, Hm, Wm)
+    for key, prev_map in (("local", prev_emb), ("local_proxy", proxy_map)):
+        pm = ops.resize_bilinear_hwc(prev_map, Hm, Wm, float16=f16) if cfg.MODEL_LOCAL_DOWNSAMPLE else prev_map
+        lf = ops.local_window_match(qm, pm, right_prev, radii, fr.bias, O, True, atrous_rate=lrate, float16=f16)        # [O, nl, Hm, Wm]
+        ops.resize_bilinear_planes(lf.view(O * nl, Hm, Wm), h, w, base[ch[key] * hw:], hw, 1, inner_count=nl, out_outer_stride=fr.obj_stride)
+    return k1_copies
+
+
+def correlation_sets(levels, n_obj, hw, obj_stride, ch, n_adaptive, bank_sets=None):
+    """The sets of the one correlation launch -- cluster (2 sets / object / level) + k = 1 proxy (1 set / object), AEM:316-319 + matching.py:2653 --
+    as host lists (set_begin, set_size, set_off): first row and rows of each set in the proxy table, and where its plane starts in the flat
+    proto-mask tensor (`ch` = channel_slices).  bank_sets: IncrementalProxyBank's (set_begin, set_size, ...) of its own table layout.
+    Touches no tensor and no device."""
+    kmax = max(levels)
+    if bank_sets is not None:
+        set_begin, set_size = list(bank_sets[0]), list(bank_sets[1])
+        set_off = [o * obj_stride + (ch["cluster"] + f) * hw for o in range(n_obj) for f in range(2)]
+    else:
+        where = [(l, k, o, f) for l, k in enumerate(levels) for o in range(n_obj) for f in range(2)]
+        set_begin = [((l * n_obj + o) * 2 + f) * kmax for l, k, o, f in where]
+        set_size = [k for l, k, o, f in where]              # slots >= the sticky K carry norm = +inf and are ignored
+        set_off = [o * obj_stride + (ch["cluster"] + 2 * l + f) * hw for l, k, o, f in where]
+    return (set_begin + [n_adaptive + o for o in range(n_obj)], set_size + [1] * n_obj,
+            set_off + [o * obj_stride + ch["proxy"] * hw for o in range(n_obj)])
+
+
+def set_bias_table(bias, n_levels):
+    """The bias of every set of correlation_sets: the object's, for its two sets per level and for its k = 1 set."""
+    per_level = bias.repeat_interleave(2)
+    return torch.cat([per_level.repeat(n_levels) if n_levels > 1 else per_level, bias])
+
+
+def _set_bias(fr, dis_bias, dense_state):
+    """Stage 6b: the per-set bias table (a function of the bias vector alone: kept with the sequence's state while the vector is unchanged).  The
+    cache is keyed on the CALLER's tensor; when _bias_vec had to build a new tensor (float, one element, other dtype / shape) its address says
+    nothing about its value, so nothing is cached then."""
+    L, O = len(fr.levels), fr.O
+    keyed = torch.is_tensor(dis_bias) and dis_bias.is_cuda and dis_bias.dtype == torch.float32 and dis_bias.numel() == O and dense_state is not None
+    bkey = (dis_bias.data_ptr(), dis_bias._version, L, O) if keyed else None
+    cached_bias = dense_state.get("set_bias") if keyed else None
+    if cached_bias is not None and cached_bias[0] == bkey:
+        return cached_bias[1]
+    set_bias = set_bias_table(fr.bias, L)
+    if keyed:
+        dense_state["set_bias"] = (bkey, set_bias)
+    return set_bias
+
+
+def _correlation(fr, main, ahead, k1_copies, table, sqn, sets, set_bias, query_split, defer):
+    """Stage 7: joins the chain, completes the k = 1 rows, then the one correlation launch -- or, deferred, its PendingCorrelation (else None)."""
+    set_begin, set_size, set_off = sets
+    O, ch = fr.O, fr.ch
+    if ahead is not None:
+        main.wait_event(ahead.done_event)   # join: the proxy table is complete
+    for src, dst in k1_copies:              # (no local-prep launch took them along)
+        dst.copy_(src)
+    if fr.f16:
+        # cluster channels: the constant 1 (every cluster distance is the reference's 5e4 padding); k = 1 proxies in the `.half()` arithmetic
+        fr.feat[:, ch["cluster"]:ch["cluster"] + 2 * len(fr.levels)].fill_(1.0)
+        ops.proxy_corr_min(fr.query_flat, table, None, set_begin[-O:], set_size[-O:], set_off[-O:], fr.bias, fr.feat, 1, True, float16=True)
+    elif defer:
+        pending = PendingCorrelation()
+        pending.query, pending.table, pending.sqn, pending.set_bias, pending.feat = fr.query_flat, table, sqn, set_bias, fr.feat
+        pending.query_split, pending.set_begin, pending.set_size, pending.set_off = query_split, set_begin, set_size, set_off
+        pending.stream = main
+        pending.ready = torch.cuda.Event()
+        pending.ready.record(main)
+        return pending
+    elif query_split is not None:
+        # the fp16-split correlation kernel (fp32-equivalent, device-side take-over to exact fp32), also for one frame per launch: with
+        # hundreds of proxies (cfg3: 1158, cfg4: 1161) the exact-fp32 MFMA kernel is ten times slower; "fp32" asks for that kernel
+        ops.proxy_corr_min_records([(fr.query_flat, query_split, table, sqn, set_bias, fr.feat)], set_begin, set_size, set_off, True)
+    else:
+        ops.proxy_corr_min_batched([(fr.query_flat, table, sqn, set_bias, fr.feat)], set_begin, set_size, set_off, True,
+                                   "fp32" if fr.precision == "fp32" else "split")
+    return None
+
+
+def _finish(fr, main, dense_done, prev_flat_labels, ref_pos, ref_neg, prev_pos, prev_neg):
+    """Stage 8: joins the dense stream, then the previous-frame mask channel (aocnet.py:356), the background maps (AEM:9-23, aocnet.py:349-353)
+    and the attention head (ATT:188) in one launch -> attention_head."""
+    if dense_done is not None:
+        main.wait_event(dense_done)           # join: channel 0 (dense) is complete
+    ch, bg = fr.ch, fr.cfg.MODEL_MATCHING_BACKGROUND
+    return ops.proto_finish(fr.feat, fr.hw, fr.obj_stride, ch["local"], fr.nl, ch["local_bg"] if bg else -1, ch["global_fg"], ch["global_bg"] if bg else -1,
+                            ch["prev_mask"], prev_flat_labels, ref_pos.contiguous(), ref_neg.contiguous(), prev_pos, prev_neg)
 
 
 def proto_mask_features(cfg, ref_emb, ref_labels, prev_emb, prev_labels, cur_emb, dis_bias, init_rows=None,
@@ -301,203 +545,26 @@ def proto_mask_features(cfg, ref_emb, ref_labels, prev_emb, prev_labels, cur_emb
     (ops.atrous_subsample of every pool frame, AEM:533-579): the dense and cluster matchings (and a cluster_ahead) see THAT pool, the pooled
     heads the full one.
     """
-    R, h, w, C = ref_emb.shape
-    O = ref_labels.shape[-1]
-    hw = h * w
-    dev = cur_emb.device
-    nl = len(cfg.MODEL_MULTI_LOCAL_DISTANCE)
-    ch = channel_slices(cfg)
-    n_ch = cfg.proto_channels
-    bias = _bias_vec(dis_bias, O, dev)
-    feat = torch.empty(O, n_ch, h, w, dtype=torch.float32, device=dev)
-    base = feat.view(-1)
-    obj_stride = n_ch * hw
-    f16 = bool(cfg.MODEL_FLOAT16_MATCHING)
-    lrate = max(1, int(cfg.TEST_LOCAL_ATROUS_RATE))
     m_emb, m_lab = match_pool if match_pool is not None else (ref_emb, ref_labels)
-    pool = m_emb.reshape(-1, C)                                 # what the dense and cluster matchings see
-    labels_flat = m_lab.reshape(-1, O)
-    query_flat = cur_emb.reshape(hw, C)
-    levels = cfg.cluster_levels
-    L, kmax = len(levels), max(levels)
-    n_ad = L * O * 2 * kmax
-    if cluster_ahead is not None and cluster_ahead.cluster_sets is not None:
-        n_ad = cluster_ahead.cluster_sets[2]             # IncrementalProxyBank: its own table layout
-
-    # ---- adaptive proxies (k-means, AEM:252-286) + k = 1 proxies (ATT:155-189) in ONE proxy table
+    fr = _Frame(cfg, ref_emb, ref_labels, m_emb, m_lab, cur_emb, dis_bias, dense_precision, cluster_ahead)
     main = torch.cuda.current_stream()
+    # 1. adaptive proxies (k-means, AEM:252-286) and the k = 1 proxies (ATT:155-189) share ONE proxy table
     if cluster_ahead is None and cluster_state is not None:
         # host-sync-free variant: the chain is enqueued here (on side_stream when given) and joined in front of the correlation launch
         cluster_ahead = launch_cluster_proxies(cfg, m_emb, m_lab, cluster_state["init_rows"], side_stream)
-    if cluster_ahead is not None:
-        assert cluster_ahead.R == R, "cluster_ahead was launched for another pool size"
-        main.wait_event(cluster_ahead.prep_event)
-        table, sqn, prep, cp = cluster_ahead.table, cluster_ahead.sqn, cluster_ahead.prep, cluster_ahead.aux
-        for t in (table, sqn, prep.right_bits, prep.wrong_bits, prep.fg_rows, prep.obj_rows, prep.counts, prep.obj_offsets):
-            t.record_stream(main)
-    else:
-        table = torch.empty(n_ad + O, C, dtype=torch.float32, device=dev)
-        sqn = torch.empty(n_ad + O, dtype=torch.float32, device=dev)
-        # (float16 matching: no clustering at all -- scipy rejects float16 data and the reference's cluster channels are the constant 1)
-        cp = cluster_proxies(pool, labels_flat, levels if cfg.CLUSTER_LEVELS else levels[0], init_rows, rng) if not f16 else None
-        prep = cp["prep"] if cp is not None else ops.label_prep(labels_flat)
-        if cp is not None:
-            table[:n_ad].copy_(cp["proxies"].reshape(-1, C))
-            sqn[:n_ad].copy_(cp["proxy_sqnorm"].reshape(-1))
-        else:
-            sqn[:n_ad].fill_(float("inf"))       # nothing labelled -> every cluster feature is 1
-
-    cached = dense_state.get("ref_pool") if dense_state is not None else None
-    k1_copies = []
-    if cached is not None and cached[0] == R:
-        # the pooled reference heads are a function of the pool alone (ATT:155-170): unchanged since the last frame
-        _, ref_pos, ref_neg, ref_sq = cached
-        k1_copies = [(ref_pos, table[n_ad:]), (ref_sq, sqn[n_ad:])]       # into the k = 1 rows of this frame's proxy table (by the local-prep launch)
-    else:
-        ref_pos, ref_neg = ops.masked_mean_pool(ref_emb.reshape(R, hw, C), ref_labels.reshape(R, hw, O), cfg.MODEL_EPSILON, pixel_major=True,
-                                                out_pos=table[n_ad:], out_pos_sqnorm=sqn[n_ad:])
-        if dense_state is not None:
-            dense_state["ref_pool"] = (R, ref_pos.clone(), ref_neg, sqn[n_ad:].clone())
-    prev_pos, prev_neg = ops.masked_mean_pool(prev_emb.reshape(1, hw, C), prev_labels.reshape(1, hw, O), cfg.MODEL_EPSILON, pixel_major=True)
-
-    # ---- dense pixel-level matching, AEM:688-817 -> channel 0
-    pool_split = None
-    if f16:
-        dense_precision = "f16"                              # AEM:801-803 on float16 tensors
-    if dense_state is not None and (dense_precision or ops.DENSE_PRECISION) == "split" and ops.split_record_bytes(C):
-        pool_split = dense_state.get("pool_split")
-        done = dense_state.get("frames", 0)
-        mhw = pool.shape[0] // R
-        if pool_split is None or pool_split.records.shape[0] < R * mhw:
-            cap = max(R, dense_state.get("capacity_frames", R)) * mhw
-            pool_split = ops.SplitRows()
-            pool_split.records = torch.empty(cap, ops.split_record_bytes(C), dtype=torch.uint8, device=dev)
-            pool_split.sqnorm = torch.empty(cap, dtype=torch.float32, device=dev)
-            pool_split.overflow = torch.zeros(1, dtype=torch.int32, device=dev)
-            pool_split.n = cap
-            done = 0
-        if done < R:
-            ops.split_rows(pool[done * mhw:R * mhw], out=pool_split, row0=done * mhw)
-        # records of pool frames [0, max(done, R)) are valid; a caller that restarts the pool (new sequence) resets "frames" to 0
-        dense_state["pool_split"], dense_state["frames"] = pool_split, max(done, R)
-    # the query's split records, ONCE per frame and tile-major: the dense kernel and the correlation kernel both stream them in their MFMA
-    # operand layout (the correlation kernel reads the fp32 rows only on its exact-fp32 take-over)
-    query_split = None
-    if (dense_precision or ops.DENSE_PRECISION) == "split" and ops.split_record_bytes(C) and C == 100 and prep.n_obj <= 16:
-        query_split = ops.split_rows(query_flat, overflow=pool_split.overflow if pool_split is not None else None, tiled=True)
-    dense_done = None
-    if dense_stream is not None:
-        main = torch.cuda.current_stream()
-        dense_stream.wait_stream(main)
-        with torch.cuda.stream(dense_stream):
-            ops.dense_match(query_flat, pool, prep, bias, feat, 1, obj_stride, True, precision=dense_precision, query_split=query_split,
-                            pool_split=pool_split)
-            dense_done = torch.cuda.Event()
-            dense_done.record(dense_stream)
-        feat.record_stream(dense_stream)
-        if query_split is not None:
-            query_split.records.record_stream(dense_stream)
-            query_split.sqnorm.record_stream(dense_stream)
-    else:
-        ops.dense_match(query_flat, pool, prep, bias, feat, 1, obj_stride, True, precision=dense_precision, query_split=query_split,
-                        pool_split=pool_split)
-
-    # ---- local matching against the previous frame and against its per-pixel proxy map (aocnet.py:255,325-337)
-    radii = list(cfg.MODEL_MULTI_LOCAL_DISTANCE)
-    prev_flat_labels = prev_labels.reshape(hw, O)
-    if cfg.MODEL_LOCAL_DOWNSAMPLE and not f16 and lrate == 1:
-        # one launch for the three bilinear down-samples, the (never materialised) proxy map and the label bits; one for both matchings;
-        # one for both up-samples into their channel ranges
-        H2, W2 = int(h / 2) + 1, int(w / 2) + 1
-        q2, p2, pm2, bits2 = ops.local_prep(cur_emb, prev_emb, prev_flat_labels, prev_pos, H2, W2, copies=k1_copies)
-        k1_copies = []
-        lf = ops.local_window_match_pair(q2, p2, pm2, bits2, radii, bias, O, True)          # [2, O, nl, H2, W2]
-        ops.resize_bilinear_planes_grouped(lf.view(2 * O * nl, H2, W2), h, w, base[ch["local"] * hw:], nl, O, (ch["local_proxy"] - ch["local"]) * hw,
-                                           obj_stride, hw, 1)
-    else:
-        # matching.local_matching / local_matching_proxy step by step (AEM:968-1060): full resolution (MODEL_LOCAL_DOWNSAMPLE off), the float16
-        # arithmetic (down-samples of float16 tensors), the atrous window stride
-        right_prev, _ = ops.label_bits(prev_flat_labels, want_wrong=False)
-        proxy_map = ops.label_mix(prev_flat_labels, prev_pos).view(h, w, C)                # aocnet.py:325
-        Hm, Wm, qm = h, w, cur_emb
-        if cfg.MODEL_LOCAL_DOWNSAMPLE:
-            Hm, Wm = int(h / 2) + 1, int(w / 2) + 1
-            qm = ops.resize_bilinear_hwc(cur_emb, Hm, Wm, float16=f16)
-            right_prev = ops.resize_nearest_bits(right_prev, h, w, Hm, Wm)
-        for key, prev_map in (("local", prev_emb), ("local_proxy", proxy_map)):
-            pm = ops.resize_bilinear_hwc(prev_map, Hm, Wm, float16=f16) if cfg.MODEL_LOCAL_DOWNSAMPLE else prev_map
-            lf = ops.local_window_match(qm, pm, right_prev, radii, bias, O, True, atrous_rate=lrate, float16=f16)        # [O, nl, Hm, Wm]
-            ops.resize_bilinear_planes(lf.view(O * nl, Hm, Wm), h, w, base[ch[key] * hw:], hw, 1, inner_count=nl, out_outer_stride=obj_stride)
-
-    # ---- one correlation launch: cluster (2 sets / object / level) + k = 1 proxy (1 set / object), AEM:316-319 + matching.py:2653
-    set_begin, set_size, set_off, set_obj = [], [], [], []
-    if cluster_ahead is not None and cluster_ahead.cluster_sets is not None:
-        set_begin, set_size = list(cluster_ahead.cluster_sets[0]), list(cluster_ahead.cluster_sets[1])
-        for o in range(O):
-            for f in range(2):
-                set_off.append(o * obj_stride + (ch["cluster"] + f) * hw)
-                set_obj.append(o)
-    else:
-        for l, k in enumerate(levels):
-            for o in range(O):
-                for f in range(2):
-                    set_begin.append(((l * O + o) * 2 + f) * kmax)
-                    set_size.append(k)                      # slots >= the sticky K carry norm = +inf and are ignored
-                    set_off.append(o * obj_stride + (ch["cluster"] + 2 * l + f) * hw)
-                    set_obj.append(o)
-    for o in range(O):
-        set_begin.append(n_ad + o)
-        set_size.append(1)
-        set_off.append(o * obj_stride + ch["proxy"] * hw)
-        set_obj.append(o)
-    # per-set bias table (a function of the bias vector alone: kept with the sequence's state while the vector is unchanged).  The cache is
-    # keyed on the CALLER's tensor; when _bias_vec had to build a new tensor (float, one element, other dtype / shape) its address says nothing
-    # about its value, so nothing is cached then
-    src = dis_bias if (torch.is_tensor(dis_bias) and dis_bias.is_cuda and dis_bias.dtype == torch.float32 and dis_bias.numel() == O) else None
-    bkey = (src.data_ptr(), src._version, L, O) if src is not None else None
-    cached_bias = dense_state.get("set_bias") if (dense_state is not None and bkey is not None) else None
-    if cached_bias is not None and cached_bias[0] == bkey:
-        set_bias = cached_bias[1]
-    else:
-        set_bias = bias.repeat_interleave(2).repeat(L) if L > 1 else bias.repeat_interleave(2)
-        set_bias = torch.cat([set_bias, bias])
-        if dense_state is not None and bkey is not None:
-            dense_state["set_bias"] = (bkey, set_bias)
-    if cluster_ahead is not None:
-        torch.cuda.current_stream().wait_event(cluster_ahead.done_event)   # join: the proxy table is complete
-    for src, dst in k1_copies:                        # (no local-prep launch took them along)
-        dst.copy_(src)
-    pending = None
-    if f16:
-        # cluster channels: the constant 1 (every cluster distance is the reference's 5e4 padding); k = 1 proxies in the `.half()` arithmetic
-        n_cl = 2 * L
-        feat[:, ch["cluster"]:ch["cluster"] + n_cl].fill_(1.0)
-        ops.proxy_corr_min(query_flat, table, None, [n_ad + o for o in range(O)], [1] * O, [o * obj_stride + ch["proxy"] * hw for o in range(O)], bias, feat, 1,
-                           True, float16=True)
-    elif defer_correlation:
-        pending = PendingCorrelation()
-        pending.query, pending.table, pending.sqn, pending.set_bias, pending.feat = query_flat, table, sqn, set_bias, feat
-        pending.query_split = query_split
-        pending.set_begin, pending.set_size, pending.set_off = set_begin, set_size, set_off
-        pending.stream = torch.cuda.current_stream()
-        pending.ready = torch.cuda.Event()
-        pending.ready.record(pending.stream)
-    else:
-        # the fp16-split correlation kernel (fp32-equivalent, device-side take-over to exact fp32), also for one frame per launch: with
-        # hundreds of proxies (cfg3: 1158, cfg4: 1161) the exact-fp32 MFMA kernel is ten times slower; "fp32" asks for that kernel
-        if query_split is not None:
-            ops.proxy_corr_min_records([(query_flat, query_split, table, sqn, set_bias, feat)], set_begin, set_size, set_off, True)
-        else:
-            ops.proxy_corr_min_batched([(query_flat, table, sqn, set_bias, feat)], set_begin, set_size, set_off, True,
-                                       "fp32" if (dense_precision or ops.DENSE_PRECISION) == "fp32" else "split")
-
-    if dense_done is not None:
-        torch.cuda.current_stream().wait_event(dense_done)           # join: channel 0 (dense) is complete
-    # ---- previous-frame mask channel (aocnet.py:356), background maps (AEM:9-23, aocnet.py:349-353) and the attention head (ATT:188) in one launch
-    bg = cfg.MODEL_MATCHING_BACKGROUND
-    attention_head = ops.proto_finish(feat, hw, obj_stride, ch["local"], nl, ch["local_bg"] if bg else -1, ch["global_fg"], ch["global_bg"] if bg else -1,
-                                      ch["prev_mask"], prev_flat_labels, ref_pos.contiguous(), ref_neg.contiguous(), prev_pos, prev_neg)
-    return feat, attention_head, dict(cluster=cp, prev_pos=prev_pos, ref_pos=ref_pos, pending_correlation=pending)
+    table, sqn, prep, cp = _proxies_ahead(fr, main, cluster_ahead) if cluster_ahead is not None else _proxies_inline(fr, init_rows, rng)
+    # 2 .. 5
+    ref_pos, ref_neg, prev_pos, prev_neg, k1_copies = _pooled_heads(fr, ref_emb, ref_labels, prev_emb, prev_labels, table, sqn, dense_state)
+    pool_split, query_split = _split_records(fr, prep, dense_state)
+    dense_done = _dense_matching(fr, main, prep, query_split, pool_split, dense_stream)
+    prev_flat_labels = prev_labels.reshape(fr.hw, fr.O)
+    k1_copies = _local_matching(fr, cur_emb, prev_emb, prev_flat_labels, prev_pos, k1_copies)
+    # 6. the plan of the one correlation launch; 7. the launch behind the chain's done_event; 8. the rest behind the dense stream's event
+    sets = correlation_sets(fr.levels, fr.O, fr.hw, fr.obj_stride, fr.ch, fr.n_ad, cluster_ahead.cluster_sets if cluster_ahead is not None else None)
+    set_bias = _set_bias(fr, dis_bias, dense_state)
+    pending = _correlation(fr, main, cluster_ahead, k1_copies, table, sqn, sets, set_bias, query_split, defer_correlation)
+    attention_head = _finish(fr, main, dense_done, prev_flat_labels, ref_pos, ref_neg, prev_pos, prev_neg)
+    return fr.feat, attention_head, dict(cluster=cp, prev_pos=prev_pos, ref_pos=ref_pos, pending_correlation=pending)
 
 
 class FrameRunner:
@@ -540,9 +607,7 @@ class FrameRunner:
         # (with cfg.TEST_GLOBAL_ATROUS_RATE > 1 the ClusterProxiesAhead -- label prep and k-means chain -- is the one of match_pool(ref_emb, ref_labels))
         O = ref_labels.shape[-1]
         bias = _bias_vec(dis_bias, O, cur_emb.device)
-        main = torch.cuda.current_stream()
-        for t in (a.table, a.sqn, a.prep.right_bits, a.prep.wrong_bits, a.prep.fg_rows, a.prep.obj_rows, a.prep.counts, a.prep.obj_offsets):
-            t.record_stream(main)
+        a.read_on(torch.cuda.current_stream())
         return self.call(ref_emb, ref_labels, prev_emb, prev_labels, cur_emb, bias, a.prep, a.table, a.sqn, a.prep_event, a.done_event, pool_key, probes, pool_prefix_frames)
 
 

@@ -220,6 +220,10 @@ class LabelPrep:
     """Result of aoc_label_prep (all device tensors)."""
     __slots__ = ("n", "n_obj", "right_bits", "wrong_bits", "fg_rows", "obj_rows", "counts", "obj_offsets")
 
+    def tensors(self):
+        """The six lists, in the order of _prep_lists."""
+        return self.right_bits, self.wrong_bits, self.fg_rows, self.obj_rows, self.counts, self.obj_offsets
+
 
 def label_prep(labels_flat):
     labels_flat = _f32c(labels_flat)
@@ -1040,6 +1044,11 @@ class _ChainDesc(ctypes.Structure):
 CHAIN_MAX_FRAMES = 8      # frames one aoc_chain_desc names (tables[8] / sqnorms[8])
 
 
+def _adaptive_rows(levels, n_obj):
+    """Rows of the adaptive part of a proxy table: levels x objects x (centroid | centroid_avg) x kmax."""
+    return len(levels) * n_obj * 2 * int(max(levels))
+
+
 def cluster_chain(pool, prep, levels, init_rows, tables, sqnorms, iters=20):
     """aoc_cluster_chain_enqueue: the k-means chain of len(tables) frames that see one pool state -- replicated lists with sticky K, 20 Lloyd
     iterations, proxy construction, every frame's proxies scattered into ITS table -- as ONE C call out of one workspace (on the current stream,
@@ -1049,7 +1058,7 @@ def cluster_chain(pool, prep, levels, init_rows, tables, sqnorms, iters=20):
     pool = _a16("cluster_chain: pool", _f32c(pool))
     _need_gpu(pool, init_rows, *tables, *sqnorms)
     F, L, O, C = len(tables), len(levels), prep.n_obj, pool.shape[1]
-    kmax = int(max(levels))
+    kmax, n_ad = int(max(levels)), _adaptive_rows(levels, O)
     init_rows = _i32c(init_rows)
     _, _, fg_rows, obj_rows, _, obj_offsets = _prep_lists(prep)
     if not (1 <= F <= CHAIN_MAX_FRAMES and 1 <= L <= 8 and len(sqnorms) == F and init_rows.numel() == F * L * O * kmax):
@@ -1062,11 +1071,11 @@ def cluster_chain(pool, prep, levels, init_rows, tables, sqnorms, iters=20):
     d.pool, d.fg_rows, d.obj_rows, d.obj_offsets, d.init_rows = _addr(pool), _addr(fg_rows), _addr(obj_rows), _addr(obj_offsets), _addr(init_rows)
     for f in range(F):
         table, sqn = tables[f], sqnorms[f]
-        if table.dim() != 2 or table.shape[0] < L * O * 2 * kmax:
-            raise ValueError(f"cluster_chain: tables[{f}] {tuple(table.shape)} has fewer than {L * O * 2 * kmax} rows")
+        if table.dim() != 2 or table.shape[0] < n_ad:
+            raise ValueError(f"cluster_chain: tables[{f}] {tuple(table.shape)} has fewer than {n_ad} rows")
         _out(f"cluster_chain: tables[{f}]", table, (table.shape[0], C))
         _a16(f"cluster_chain: tables[{f}]", table, output=True)
-        _span(f"cluster_chain: sqnorms[{f}]", sqn, L * O * 2 * kmax)
+        _span(f"cluster_chain: sqnorms[{f}]", sqn, n_ad)
         d.tables[f], d.sqnorms[f] = _addr(table), _addr(sqn)
     lib = _lib.lib()
     ws = _ws(lib.aoc_cluster_chain_workspace_bytes(ctypes.byref(d)), pool.device)
@@ -1167,7 +1176,7 @@ class FrameCall:
         for i, k in enumerate(levels):
             d.levels[i] = int(k)
         d.matching_background = int(bool(matching_background))
-        d.n_adaptive = len(levels) * self.n_obj * 2 * max(levels)
+        d.n_adaptive = _adaptive_rows(levels, self.n_obj)
         d.epsilon = float(epsilon)
         d.float16_matching, d.local_downsample, d.local_atrous_rate = int(bool(float16_matching)), int(bool(local_downsample)), int(local_atrous_rate)
         # TEST_GLOBAL_ATROUS_RATE > 1: the dense and cluster matchings see every pool frame on the atrous grid (AEM:533-579); the sub-sampled pool is
@@ -1214,7 +1223,7 @@ class FrameCall:
         _need_gpu(ref_emb, ref_labels, prev_emb, prev_labels, cur_emb, dis_bias, table, sqn)
         for t in (ref_emb, ref_labels, prev_emb, prev_labels, cur_emb, dis_bias, table, sqn):
             assert t.dtype == torch.float32 and t.is_contiguous(), "aoc_frame_enqueue takes contiguous float32 tensors"
-        right_bits, wrong_bits, fg_rows, obj_rows, counts, obj_offsets = prep.right_bits, prep.wrong_bits, prep.fg_rows, prep.obj_rows, prep.counts, prep.obj_offsets
+        right_bits, wrong_bits, fg_rows, obj_rows, counts, obj_offsets = prep.tensors()
         for t in (right_bits, wrong_bits, fg_rows, obj_rows, counts, obj_offsets):
             assert t.dtype == torch.int32 and t.is_contiguous(), "aoc_frame_enqueue takes the contiguous int32 lists of ops.label_prep"
         # class-16 pointers of aoc_frame_desc: the three embeddings are inputs (copied when off the grid), the proxy table is also written
