@@ -391,10 +391,26 @@ def run_interleaved(specs_data, device, lanes, backend_factory=None, dense_preci
             b.lane = l                  # a factory does not know its lane: without this every backend would share lane 0's cached side stream
         backends.append(b)
     metrics = [_default_metric(device) for _ in range(n_lanes)]
-    running = [None] * n_lanes
-    frames = objects = 0
-    keep = []                                       # the sequences' tensors stay alive until the last lane has drained
     torch.cuda.synchronize(device)
+    # the sequences' tensors stay alive (in `taken`) until the last lane has drained
+    taken = round_robin(todo, n_lanes, stagger, lambda l, item: sequence_steps(item[0], backends[l], metrics[l], item[1]),
+                        lambda l: torch.cuda.stream(streams[l]))
+    torch.cuda.synchronize(device)
+    frames = sum(data[0].shape[0] - 1 for _, _, (_, data) in taken)
+    objects = sum((data[0].shape[0] - 1) * (spec.n_obj - 1) for _, _, (spec, data) in taken)
+    tot = [m.totals() for m in metrics]
+    return dict(frames=frames, objects=objects, sum_iou=sum(t["sum_j"] for t in tot), sum_f=sum(t["sum_f"] for t in tot),
+                iou_count=sum(t["objects"] for t in tot))
+
+
+def round_robin(items, n_lanes, stagger, begin, lane_context):
+    """run_interleaved's bookkeeping, without a device: the lanes take turns in passes; a free lane takes the next item off the list
+    (``begin(lane, item)`` -> the iterator of its steps) and advances it one step in the same turn, every other turn advances the lane's item
+    by one step, and a lane learns that its item has ended in a turn of its own (it takes the next item one pass later).  Every turn runs
+    inside ``lane_context(lane)``.  Returns [(pass, lane, item)] in the order the items were taken; the passes count from 1."""
+    todo = list(items)
+    running = [None] * n_lanes
+    taken = []
     n_pass = 0
     while True:
         busy = False
@@ -405,23 +421,18 @@ def run_interleaved(specs_data, device, lanes, backend_factory=None, dense_preci
                 # pool changes (row-count read-back, host draws, a k-means chain nothing else of the lane overlaps) on the same pass
                 busy = True
                 continue
-            with torch.cuda.stream(streams[l]):
+            with lane_context(l):
                 if running[l] is None and todo:
-                    spec, data = todo.pop(0)
-                    keep.append(data)
-                    frames += data[0].shape[0] - 1
-                    objects += (data[0].shape[0] - 1) * (spec.n_obj - 1)
-                    running[l] = sequence_steps(spec, backends[l], metrics[l], data)
+                    item = todo.pop(0)
+                    taken.append((n_pass, l, item))
+                    running[l] = begin(l, item)
                 if running[l] is not None:
                     busy = True
                     if next(running[l], None) is None:
                         running[l] = None
         if not busy:
             break
-    torch.cuda.synchronize(device)
-    tot = [m.totals() for m in metrics]
-    return dict(frames=frames, objects=objects, sum_iou=sum(t["sum_j"] for t in tot), sum_f=sum(t["sum_f"] for t in tot),
-                iou_count=sum(t["objects"] for t in tot))
+    return taken
 
 
 def eval_sharded(specs: Sequence[SequenceSpec], rank: int, world: int, device, backend=None, metric=None, max_frames=None, barrier=None, lanes=1, stagger=1):

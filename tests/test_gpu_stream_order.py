@@ -15,6 +15,7 @@ the library's wrappers, and an early read of an unwritten list can address outsi
 import pytest
 import torch
 
+import lane_cases
 import stream_order_cases as soc
 from stream_order_cases import H, W, C, Ctx, assert_same, snapshot, stalled_equals_serial
 
@@ -520,48 +521,7 @@ def test_pending_correlation_tensors_outlive_the_frame(so):
 
 
 # ------------------------------------------------------------------------------------------ h. the evaluation runner
-def _backend_class(er):
-    class StalledBackend(er.HotPathBackend):
-        """HotPathBackend whose side stream is given by the test and stalled (ctx) in front of every chain it launches; gt_frames: frames whose
-        ground truth reaches the memory policy (the pool changes earlier than the chains launched ahead assumed); pool_capacity: frames the
-        resident pool tensor starts with (1: _reference_pool has to grow it)."""
-
-        def __init__(self, device, side, ctx=None, pool_capacity=None, chain_plan=None, consumer=None):
-            super().__init__(device)
-            self.side, self.ctx, self.pool_capacity, self.consumer = side, ctx, pool_capacity, consumer
-            self.stalled_now, self.t_frame = False, 0.0
-            if chain_plan is not None:
-                self.chain_plan = list(chain_plan)
-
-        def start(self, spec):
-            super().start(spec)
-            self._head(self.mc.proto_channels)               # its upload waits for the stream: here, not under the first frame's stall
-            torch.cuda.synchronize()
-            if self.pool_capacity is not None:
-                self._pool_emb, self._pool_lab = self._pool_emb[:self.pool_capacity].clone(), self._pool_lab[:self.pool_capacity].clone()
-
-        def _launch_batch(self, *args):
-            if self.ctx is not None:
-                self.ctx.stall(self.side)
-                self.ctx.probe(self.consumer if self.consumer is not None else torch.cuda.current_stream())
-                self.stalled_now = True
-            return super()._launch_batch(*args)
-
-        def _lane_logits(self, emb):
-            import time
-            t0 = time.perf_counter()
-            out = super()._lane_logits(emb)
-            self.t_frame = max(self.t_frame, time.perf_counter() - t0)
-            if self.stalled_now:                             # this frame's enqueue is complete and its chain has not begun
-                self.ctx.still_stalled()
-                self.stalled_now = False
-            return out
-
-        def frame_with_gt(self, emb, gt):
-            h, w = self.spec.h, self.spec.w
-            logit = torch.nn.functional.interpolate(self._lane_logits(emb)[None], size=(4 * h, 4 * w), mode="bilinear", align_corners=True)[0]
-            return self.policy.update(emb, torch.softmax(logit, dim=0), gt_label=gt)[0]
-    return StalledBackend
+_backend_class = lane_cases.stalled_backend_class          # StalledBackend: shared with test_gpu_eval_lanes.py
 
 
 def _label_maps(be, spec, data, gt_frames=()):
